@@ -21,11 +21,20 @@ round-robin (pt_set_row_partition); per frame every rank exchanges the 2 accumul
 below its bands with its band neighbours (RCCL P2P), runs screenOutput on its own bands into a
 canvas over a torch tensor, and the RGBA8 bands are gathered to rank 0 (RCCL, asynchronous, under
 the next frame). Every libpt draw and every torch/RCCL op of a rank is ordered on one dedicated
-torch stream (not the legacy default stream). Rank 0 then measures the same frame over the same GPUs
-through one multi-part context (`--engine multipart`: libpt's own fan-out, peer copies, no RCCL) in a
-child process and adds it to the line as `multipart`.
+torch stream (not the legacy default stream).
 
-At N = 1 the line also carries the roofline of the path tracing: algorithmic bytes per frame (SURVEY.md
+A plain run sets up, warms up, times --steps steps, writes its outputs when --dump-outputs DIR is given
+(what the last timed step left a caller: DIR/canvas.npy and, at N = 1, DIR/accumulation.npy, float32; the
+inputs are seeded, so two runs with the same arguments render the same frames) and prints the line with the
+headline (metric, value, unit, higher_is_better, dtype, ms_per_step) and the kernel timing of the timed
+region. Everything below is measured after the timed steps and only with --full.
+
+With --full at N > 1, rank 0 then measures the same frame over the same GPUs
+through one multi-part context (`--engine multipart`: libpt's own fan-out, peer copies, no RCCL) in a
+child process and adds it to the line as `multipart`; the recorded frames are replayed through the N-GPU
+route and compared bit for bit with a one-GPU render (`n_gpu_bitexact`), and the collectives are timed alone.
+
+With --full at N = 1 the line also carries the roofline of the path tracing: algorithmic bytes per frame (SURVEY.md
 §8d, counted exactly by a counting replay of the same frames) over ms_per_step against 8 TB/s, the
 L2-to-fabric traffic and VALU instructions of pt_trace + pt_cont measured live by rocprofv3 --pmc passes
 (FETCH_SIZE, WRITE_SIZE, SQ_INSTS_VALU) over 5 frames of the same workload, the bound those fractions
@@ -403,6 +412,25 @@ def timed_region(engine, step, first, count, event_every, barrier_sync, program)
                      "screen_output": round(out_ms / n, 4)}, pt_n, lat
 
 
+DUMP_ARRAY_BYTES = 30 * 10 ** 6   # --dump-outputs: per array (two arrays stay under 64 MB in all)
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: each array (H, W, 4) as <directory>/<name>.npy in float32. One larger than
+    DUMP_ARRAY_BYTES is cut to a fixed sample of its pixels, (n, 4): the same seeded, sorted pixel
+    indices for a given frame size, so two runs with the same arguments store the same pixels."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        keep = DUMP_ARRAY_BYTES // (4 * a.shape[-1])
+        pixels = a.reshape(-1, a.shape[-1])
+        if pixels.shape[0] > keep:
+            idx = np.sort(np.random.default_rng(20240229).choice(pixels.shape[0], keep, replace=False))
+            a = pixels[idx]
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def kernel_name(layout, program, workload):
     return "pt_trace<%s%s%s>" % ({"pairs": "PAIRS+", "trail": "TRAIL+"}.get(layout, ""), program.upper(),
                                  "+TEX" if workload == "helmet" else "")
@@ -628,8 +656,11 @@ def multipart_main(args, event_every):
     if args.dump_canvas:
         import numpy as np
         np.save(args.dump_canvas, engine.read_canvas(W, Hh))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"canvas": engine.read_canvas(W, Hh),
+                                         "accumulation": player.textures["pathTracingRenderTarget"].read()})
     check = None
-    if len(devs) > 1 and not args.no_check:
+    if args.full and len(devs) > 1 and not args.no_check:
         # the recorded frames again (the first clears the history) through the parts, against one GPU
         idx = list(range(PARITY_FRAMES))
         for i in idx:
@@ -669,7 +700,7 @@ def multipart_child(args, world, W, Hh):
     steps = min(args.steps, 100)
     cmd = [sys.executable, os.path.abspath(__file__), "--engine", "multipart", "--gpus", str(world),
            "--devices", ",".join(str(d) for d in range(world)), "--size", "%dx%d" % (W, Hh), "--workload", args.workload,
-           "--steps", str(steps), "--warmup", str(min(args.warmup, 10)), "--cpu-budget", "0", "--no-pmc"]
+           "--steps", str(steps), "--warmup", str(min(args.warmup, 10)), "--full", "--cpu-budget", "0", "--no-pmc"]
     if args.no_check:
         cmd.append("--no-check")
     try:
@@ -761,8 +792,15 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=100,
                     help="untimed frames first (>= 73 lets the late-bounce compaction trial finish)")
-    ap.add_argument("--cpu-budget", type=float, default=10.0, help="seconds of CPU-oracle baseline (0 = skip)")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the live rocprofv3 traffic passes")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything beside the headline: the roofline "
+                         "(counting replay, live rocprofv3 passes), the CPU baseline, the N = 1 anchor fields, and at "
+                         "N > 1 the bitwise N-GPU check, the collectives' costs and the multipart curve")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, rank 0 writes what the last timed step left a caller as DIR/<name>.npy "
+                         "(float32): the canvas and, at N = 1, the accumulation target")
+    ap.add_argument("--cpu-budget", type=float, default=10.0, help="--full: seconds of CPU-oracle baseline (0 = skip)")
+    ap.add_argument("--no-pmc", action="store_true", help="--full: skip the live rocprofv3 traffic passes")
     ap.add_argument("--no-output", action="store_true", help="time pathTracing+copy only (no screenOutput/gather)")
     ap.add_argument("--check-launch", action="store_true", help="start the ranks, report the world size, render nothing")
     ap.add_argument("--workload", choices=("dragon", "bunny", "helmet", "sky_dragon", "bunny16"), default="dragon",
@@ -778,10 +816,11 @@ def main():
                     help="N > 1: strong (default) = one 3840x2160 frame split over the GPUs (BASELINE configs[3]); "
                          "weak = N x 2.07 MP (1920x1080, 3840x1080, 3840x2160, 7680x2160)")
     ap.add_argument("--no-anchors", action="store_true",
-                    help="N = 1: skip the 4K, scan-like and converged-run fields beside the headline")
-    ap.add_argument("--no-multipart", action="store_true", help="N > 1: skip the multipart curve beside the RCCL one")
+                    help="--full, N = 1: skip the 4K, scan-like and converged-run fields beside the headline")
+    ap.add_argument("--no-multipart", action="store_true",
+                    help="--full, N > 1: skip the multipart curve beside the RCCL one")
     ap.add_argument("--no-check", action="store_true",
-                    help="N > 1: skip the bitwise check of the N-GPU frame against a one-GPU render (n_gpu_bitexact)")
+                    help="--full, N > 1: skip the bitwise check of the N-GPU frame against a one-GPU render (n_gpu_bitexact)")
     ap.add_argument("--event-every", type=int, default=None, metavar="K",
                     help="time the kernels with HIP events around every K-th frame of the timed region "
                          "(default: steps // 10, so that about 10 draws are bracketed whatever --steps is)")
@@ -806,6 +845,9 @@ def main():
         return 2
     if args.check_launch:
         return launch_check(args, world, rank)
+    if not args.full:
+        # a plain run: set up, warm up, time the steps, write the outputs, print the line
+        args.cpu_budget, args.no_pmc, args.no_anchors, args.no_multipart, args.no_check = 0.0, True, True, True, True
 
     dist, torch, stream = None, None, None
     if world > 1:
@@ -891,6 +933,13 @@ def main():
             np.save(args.dump_canvas, engine.read_canvas(W, Hh))
         elif rank == 0:
             np.save(args.dump_canvas, gather.last_frame()[:Hh].cpu().numpy())
+    if args.dump_outputs and rank == 0:
+        outs = {}
+        if not args.no_output:
+            outs["canvas"] = engine.read_canvas(W, Hh) if dist is None else gather.last_frame()[:Hh].cpu().numpy()
+        if dist is None:
+            outs["accumulation"] = player.textures["pathTracingRenderTarget"].read()
+        dump_outputs(args.dump_outputs, outs)
 
     check = None
     if dist is not None and p["parity_frames"]:
@@ -900,7 +949,7 @@ def main():
     detail = None
     if dist is not None:
         import babylon_pt as bp
-        halo_ms, gather_ms = (float("nan"), float("nan")) if args.no_output else \
+        halo_ms, gather_ms = (float("nan"), float("nan")) if args.no_output or not args.full else \
             collective_costs(dist, torch, bp, acc_t, halo, gather, world, rank)
         detail = rank_detail(dist, torch, "cuda", [kernel_ms["pathtrace"], halo_ms, gather_ms,
                                                    bp.bands_owned(Hh, world, rank)])
@@ -913,8 +962,10 @@ def main():
         ranks_seen = dist.get_world_size()
 
     comp = compaction(engine)   # (before the counting replay: counting draws never compact)
-    # algorithmic bytes of the measured frames: a counted (untimed) replay of the same frames
-    bytes_per_launch, counts = counted_frame(engine, player, args.warmup, min(args.steps, 5))
+    bytes_per_launch = counts = None
+    if args.full:
+        # algorithmic bytes of the measured frames: a counted (untimed) replay of the same frames
+        bytes_per_launch, counts = counted_frame(engine, player, args.warmup, min(args.steps, 5))
     layout = engine.bvh_layout_used()
 
     anchors = {}
@@ -945,10 +996,12 @@ def main():
         if note is None:
             traffic, valu, note = live_traffic(args.workload, W, Hh)
     ms_per_step = elapsed / args.steps * 1e3
-    roofline = roofline_object(bytes_per_launch, counts, avg_span_ms, ms_per_step, traffic, valu,
-                               "%s (+ pt_cont<...> when the draws compact) of one frame" % kernel, note)
-    roofline["kernel"] = kernel
-    roofline["bvh_walk"] = layout
+    roofline = None
+    if args.full:
+        roofline = roofline_object(bytes_per_launch, counts, avg_span_ms, ms_per_step, traffic, valu,
+                                   "%s (+ pt_cont<...> when the draws compact) of one frame" % kernel, note)
+        roofline["kernel"] = kernel
+        roofline["bvh_walk"] = layout
     line = {
         "metric": baseline_metric() if args.workload == "dragon" else METRICS[args.workload],
         "value": round(value, 2),
@@ -970,8 +1023,12 @@ def main():
         "pathtrace_span_mpaths_per_s": round(W * Hh / (avg_span_ms * 1e-3) / 1e6 * world, 2),
         **timing_fields(kernel_ms, pt_n, lat, ms_per_step, event_every),
         "late_bounce_compaction": comp,
-        "roofline": roofline,
+        "kernel": kernel,
+        "bvh_walk": layout,
+        "full": bool(args.full),
     }
+    if roofline is not None:
+        line["roofline"] = roofline
     line.update(anchors)
     if detail is not None:
         line["rank_detail"] = detail

@@ -107,6 +107,30 @@ def test_compare_frames_reports_bitwise_equality():
     assert bench.compare_frames(can[:4], acc, can, acc)["n_gpu_bitexact"] is False
 
 
+def test_dump_outputs_writes_float32_within_the_budget(tmp_path, monkeypatch):
+    """--dump-outputs: every array as <name>.npy in float32; one above the per-array budget is cut to a
+    fixed sample of its pixels - the same pixels, in order, on every run - so that the files of two
+    builds compare entry by entry."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(3)
+    can = rng.integers(0, 256, (9, 11, 4), dtype=np.uint8)
+    acc = rng.standard_normal((9, 11, 4)).astype(np.float32)
+    bench.dump_outputs(str(tmp_path / "a"), {"canvas": can, "accumulation": acc})
+    got = np.load(tmp_path / "a" / "canvas.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, can.astype(np.float32))
+    assert np.load(tmp_path / "a" / "accumulation.npy").tobytes() == acc.tobytes()
+    assert 2 * bench.DUMP_ARRAY_BYTES <= 64 * 10 ** 6
+    monkeypatch.setattr(bench, "DUMP_ARRAY_BYTES", 40 * 16)       # room for 40 of the 99 pixels
+    bench.dump_outputs(str(tmp_path / "b"), {"accumulation": acc})
+    bench.dump_outputs(str(tmp_path / "c"), {"accumulation": acc})
+    b, c = np.load(tmp_path / "b" / "accumulation.npy"), np.load(tmp_path / "c" / "accumulation.npy")
+    assert b.shape == (40, 4) and b.dtype == np.float32 and b.tobytes() == c.tobytes()
+    rows = {r.tobytes() for r in acc.reshape(-1, 4)}
+    assert all(r.tobytes() in rows for r in b)
+
+
 def test_kernel_timing_brackets_about_ten_draws():
     """HIP-event windows bracket every (steps // 10)-th frame: ~10 draws at the driver's --steps 20
     as at 200 (round 2 bracketed 2 at --steps 20); --event-every overrides."""

@@ -8,7 +8,7 @@
 #   pytest[:K[:ENV]]           the GPU parity suite (pytest -m gpu), or only the tests matching -k K (- = all),
 #                              under environment ENV (K=V[,K=V])
 #   exact                      the driver's exact bench command (bench.py --gpus 1 --steps 20 --warmup 5)
-#   bench:W[:ARGS]             bench.py --workload W (ARGS: extra bench flags, commas for spaces)
+#   bench:W[:ARGS]             bench.py --full --workload W (ARGS: extra bench flags, commas for spaces)
 #   envmx:ROUNDS:WLS:ENVS      path-tracing kernel ms per workload under environment settings, alternating
 #                              rounds (WLS comma-separated; ENVS '|'-separated, each space-free K=V[,K=V] or -)
 #   fshort:ROUNDS:WLS:ENVS     frames with the driver's short run (--steps 20 --warmup 5)
@@ -45,7 +45,7 @@ for step in "$@"; do
       if [ -n "$a1" ] && [ "$a1" != "-" ]; then run 900 "$LOG" env $envs python -u -m pytest tests -m gpu -q -rf -x --timeout 300 --timeout-method thread -k "$a1"
       else run 900 "$LOG" env $envs python -u -m pytest tests -m gpu -q -rf --timeout 300 --timeout-method thread; fi ;;
     exact) run 300 "$LOG" python3 bench.py --gpus 1 --steps 20 --warmup 5 ;;
-    bench) run 400 "$LOG" python3 bench.py --workload "$a1" ${a2//,/ } ;;
+    bench) run 400 "$LOG" python3 bench.py --full --workload "$a1" ${a2//,/ } ;;
     envmx|frames|fshort)
       : > "$LOG"; rc=0
       for r in $(seq "$a1"); do
