@@ -140,7 +140,7 @@ struct TraceArgs {
     unsigned* cont_bins;
     const unsigned* cont_perm;
     float cont_cell[3];          // the key's origin cells: (o - model box min) * cont_cell, 0..2^cont_grid_bits - 1 per axis
-    unsigned cont_grid_bits, cont_key_mode;
+    unsigned cont_grid_bits;
     Tex8 bluenoise;
     const float4* aabb;
     long long aabb_texels;
@@ -159,7 +159,6 @@ struct TraceArgs {
     // (NULL: row-major); each wave records its duration in cost[tile * 4 + quadrant]
     const unsigned* order;
     unsigned* cost;
-    unsigned prio_tiles;   // the first prio_tiles tiles of `order` (the slowest last frame) run at s_setprio 3
     unsigned order_zig;    // 1: after the split tiles, runs of 8 slots (a tile per XCD) take `order` from both
                            // ends in turn (8 slowest, 8 cheapest, ...): the slowest still start first, cheap
                            // tiles mix in
@@ -213,6 +212,19 @@ struct WfBufs {
 };
 
 constexpr unsigned kOrderHeld = 128;   // pt_order_build: tiles per thread kept in registers (a byte each)
+// the longest-first order build of a megakernel draw (pt_kernels.hip orderBuild): as its own kernel
+// (pt_order_build) or as the extra block of the next screenOutput pass (OutputArgs::ob)
+struct OrderArgs {
+    unsigned ntiles;        // 16x16 tiles of the draw
+    const unsigned* cost;   // [ntiles * 4] the waves' running durations (NULL: no build)
+    unsigned* order;        // [ntiles] out: the tiles, slowest bucket first
+    unsigned* split;        // out: how many of the first tiles of `order` the next draw splits (a multiple of 8)
+    unsigned split_cap;     // ... at most (a multiple of 8, <= ntiles)
+    unsigned dominance;     // ... when the slowest wave costs this many times the mean (0: always)
+    int near_buckets;       // ... those within this many cost buckets of the slowest
+    int flat;               // buckets more than this many below the slowest are dealt as one (-1: no flattening)
+    unsigned flat_min;      // ... for draws of more tiles than this
+};
 struct OutputArgs {
     int width, height;      // output (canvas or render target) size
     int num_parts, part;    // with an output partition: only 16-row bands b % num_parts == part
@@ -223,13 +235,9 @@ struct OutputArgs {
     float4* out_f;          // RGBA32F target (NULL when writing the canvas)
     float4* copy_dst;       // a deferred screenCopy of `acc` fused into this pass (NULL: none)
     // the longest-first order build of the last megakernel draw (pt_order_build) fused into this
-    // pass as one extra block that runs beside the output tiles (NULL ob_cost: none)
+    // pass as one extra block that runs beside the output tiles (NULL ob.cost: none)
     // (fused only while each of its 256 threads holds its tiles in registers: ntiles <= kOrderHeld * 256)
-    const unsigned* ob_cost;
-    unsigned* ob_order;
-    unsigned* ob_split;
-    unsigned ob_ntiles, ob_cap, ob_dominance;
-    int ob_near;
+    OrderArgs ob;
 };
 
 // pt_blend: the progressive accumulation of a megakernel draw (js/PathTracingCommon.js:1326-1357) over
@@ -249,13 +257,13 @@ struct BlendArgs {
 
 // (PT_CONT_SORT) pt_cont's records ordered by a ray key (pt_kernels.hip pt_cont_hist / pt_cont_scatter)
 constexpr int kSortBins = 8192;   // at most: light flag x 8 octants x 8^3 cells
+constexpr unsigned kSortChunk = 512;   // records per pt_cont_scatter workgroup (2048: ±0, 8192: -1 to -5 %)
 struct SortArgs {
     const unsigned* count;        // [0] records stored by the draw
     const unsigned short* key;    // per record (pt_trace)
     const unsigned* rank;         // per record: its place among its key's records (pt_trace)
     const unsigned* bins;         // the keys' totals
     unsigned* perm;
-    unsigned chunk;               // pt_cont_scatter: records per workgroup
     unsigned nbins;               // keys in use (a multiple of 64, <= kSortBins)
 };
 

@@ -25,13 +25,13 @@
 #include <vector>
 
 #include "pt_args.h"
+#include "pt_knobs.h"
 #include "pt_dev.h"
 
 extern "C" {
 hipError_t pt_launch_exhaustive(int op, unsigned long long* bad, hipStream_t s);
 hipError_t pt_launch_trace(int prog, int count, const pt::TraceArgs* a, int grid_x, int grid_y, hipStream_t s);
-hipError_t pt_launch_order_build(unsigned ntiles, const unsigned* cost, unsigned* order, unsigned* split,
-                                 unsigned split_cap, unsigned dominance, int near_buckets, hipStream_t s, int threads);
+hipError_t pt_launch_order_build(const pt::OrderArgs* a, hipStream_t s);
 hipError_t pt_launch_copy(const pt::CopyArgs* a, int grid_x, int grid_y, hipStream_t s);
 hipError_t pt_launch_blend(const pt::BlendArgs* a, int bands, hipStream_t s, int waves);
 hipError_t pt_launch_cont_sort(const pt::SortArgs* a, size_t cap, hipStream_t s);
@@ -120,8 +120,9 @@ struct Dev {
     // its own kernel before anything else could observe the target: flush_copy)
     struct { bool on; DevTex* src; DevTex* dst; int num_parts, part; } pending_copy = {};
     bool canvas_external = false;     // dev_canvas_wrap: caller-owned canvas memory
+    pt::Knobs k;                      // the tunables, read from the environment once (pt_knobs.h)
     int backend = PT_BACKEND_MEGAKERNEL;
-    int bvh_layout = PT_BVH_PAIRS;
+    int bvh_layout = PT_BVH_PAIRS;    // (k.bvh_layout at first; pt_set_bvh_layout)
     int bvh_used = -1;
     int cu_count = 256;
     pt::WfBufs wf = {};
@@ -129,7 +130,7 @@ struct Dev {
     size_t wf_pixels = 0, wf_slots = 0, wf_spill = 0;
     float2* mk_spill = nullptr;   // megakernel BVH stack spill slabs (one per side stream of the overlap depth)
     size_t mk_spill_lanes = 0;
-    // Frame overlap (megakernel draws; PT_OVERLAP=0 turns it off). pt_trace never reads the history:
+    // Frame overlap (megakernel draws; k.overlap). pt_trace never reads the history:
     // it writes radiance + the pre-history flag to its buffer set's rad, and pt_blend folds in the
     // history on the main stream. So draw k's path tracing runs on side stream ts[k % depth] and waits
     // only for the main stream's state when an earlier draw began (with depth 2: draw k - 1's mark, i.e.
@@ -138,28 +139,19 @@ struct Dev {
     // of this one. Per buffer set: the radiance buffer, the compaction records and the longest-first
     // cost / order / split (each set is its own longest-first pipeline, draw k ordered by the costs of
     // the set's previous draw); per side stream: the spill slab.
-    bool overlap = true;
-    // (PT_MOVING_SERIAL) frames drawn with uCameraIsMoving set run alone, one frame in flight: while the
-    // camera moves, the user sees each frame as soon as it is done instead of two frames later
-    bool moving_serial = true;
-    // Depth (PT_OVERLAP_DEPTH, 2-6): side streams; draw k waits for the mark draw k - depth - lag + 1
+    // Depth (k.depth, 2-6): side streams; draw k waits for the mark draw k - depth - lag + 1
     // recorded (depth 2, lag 0: the previous draw's), so up to `depth` frames' path tracing are in flight.
-    static constexpr int kDepthMax = 6;
-    int depth = 3;   // (r05q: three frames in flight, with compaction, won on every workload but the bunny)
-    int depth_run = 3;            // the last megakernel draw's depth (<= depth: the auto trial may pick 2)
-    bool depth_env = false;       // PT_OVERLAP_DEPTH given: the auto mode's default keeps it
-    // Lag (PT_OVERLAP_LAG): buffer sets beyond the streams. Draw k's buffer set is k % (depth + lag)
+    static constexpr int kDepthMax = pt::kDepthMax;
+    int depth_run = 3;            // the last megakernel draw's depth (<= k.depth: the auto trial may pick 2)
+    // Lag (k.lag): buffer sets beyond the streams. Draw k's buffer set is k % (depth + lag)
     // (radiance, compaction records, longest-first cost / order: what the main stream's blend, output
     // and order build read) and its stream / spill slab k % depth (what only its own stream touches),
     // and it waits for the mark of draw k - depth - lag + 1: with lag > 0 a side stream runs its next
     // draw as soon as its previous one ends, not after that draw's blend and output on the main stream.
-    // By default (lag -1) the lag is kLagSmall for draws that trace fewer than lag_pixels pixels and
-    // 0 above: a small frame (a rank's bands of an N-GPU frame) fills the chip only with more frames
-    // in flight, a 1080p one lost 3-4 % to the extra lag (r05an: 260-520 kpx +4-10 %, 1 Mpx and up -3 %).
-    static constexpr int kLagMax = 6, kSetsMax = kDepthMax + kLagMax, kLagSmall = 2;
-    int lag = -1;
+    // By default (lag -1) the lag is kLagSmall for draws that trace fewer than k.lag_pixels pixels and
+    // 0 above.
+    static constexpr int kLagMax = pt::kLagMax, kSetsMax = kDepthMax + kLagMax, kLagSmall = 2;
     int lag_run = 0;              // the last megakernel draw's lag
-    size_t lag_pixels = 800000;   // (PT_OVERLAP_LAG_PIXELS)
     hipStream_t ts[kDepthMax] = {};
     hipEvent_t ev_mark[kSetsMax] = {}, ev_traced[kDepthMax] = {};
     unsigned mk_seq = 0;          // megakernel draws so far (buffer set mk_seq % (depth + lag), stream mk_seq % depth)
@@ -167,26 +159,11 @@ struct Dev {
     unsigned mark_floor = 0;      // no draw waits for a mark older than draw mark_floor's
     float4* rad_mem = nullptr;    // rad[sets()]: radiance + flag per pixel
     size_t rad_pixels = 0;
-    // late-bounce compaction of the megakernel's mesh draws (pt_trace<P,false,true> -> pt_cont; PT_CONT:
-    // 0 off, 1 on, 2 auto - the default): per buffer set 64-B path records, their pixels and a counter; the
-    // bounce from which, and the live lanes at or below which, a wave hands its paths on; the refill batch
-    // and pt_cont's one-wave workgroups
-    int cont_mode = 2;
+    // late-bounce compaction of the megakernel's mesh draws (pt_trace<P,false,true> -> pt_cont; k.cont_mode):
+    // per buffer set 64-B path records, their pixels and a counter
     void* cont_mem = nullptr;
     size_t cont_cap = 0;          // records per buffer set ...
     int cont_sets = 0;            // ... and buffer sets allocated
-    unsigned cont_bounce = 2, cont_lanes = 48, cont_refill = 16, cont_waves = 2048;
-    // pt_cont's waves for draws that trace at least cont_big_pixels (PT_CONT_WAVES_BIG, PT_CONT_BIG_PIXELS): beside
-    // a 4K frame's path tracing fewer of them leave more wave slots to the next frames (dragon stand-in 4K
-    // +3.2 to +3.9 %, helmet 4K +0.9 %, a rank's half of the 4K frame +1.5 %, 2560x1440 +1.1 %; 1080p keeps
-    // 2048: 1536 there -1.8 %; profiles/r06bc_*, r06bd_*, r06be_*)
-    unsigned cont_waves_big = 1024;
-    size_t cont_big_pixels = 3000000;
-    bool cont_waves_env = false;
-    int cont_sort = 1;            // (PT_CONT_SORT) pt_cont takes its records ordered by a ray key (0: as stored)
-    unsigned cont_grid_bits = 2, cont_key_mode = 0;   // (PT_CONT_SORT_GRID, PT_CONT_SORT_KEY) the key's cells, field order
-    bool cont_grid_env = false;
-    unsigned sort_chunk = 512;    // (PT_CONT_SORT_CHUNK) records per pt_cont_scatter workgroup (2048: ±0, 8192: -1 to -5 %)
     // auto mode: compaction pays on the heavy 4K frames (sky + dragon +19 %, dragon stand-in +10 %) and
     // costs elsewhere (bunny 4K -22 %, helmet -9 %, rank-sized frames -29 %: profiles/r05i_*), which
     // the draw's arguments do not tell apart. So the draws of one target / program / partition time it:
@@ -207,49 +184,18 @@ struct Dev {
     // the trial starts at the 33rd draw of a target: short runs (the driver's 5 + 20 frames) stay in the
     // default, longer ones settle on the measured best
     static constexpr int kContSkip = 32, kContBlock = 10, kContSettle = 3, kContMeasured = 5, kContBlocks = 6;
-    size_t cont_auto_pixels = 2000000;   // (PT_CONT_AUTO_PIXELS) the default before the trial: on from 2 MP traced (1080p)
     hipEvent_t tune_ev[2 * kContBlocks] = {};
     int cont_last = 0;   // what the last megakernel draw did (cont_decide)
     unsigned cont_draws = 0;   // megakernel draws that launched pt_cont, since the context was created
     pt::WfBufs gb = {};           // persistent backend: per-pixel G-buffer + radiance
     void* gb_mem = nullptr;
     size_t gb_pixels = 0;
-    unsigned persist_tiles = 4;   // 8x8 wave tiles per wave (PT_PERSIST_TILES)
-    unsigned persist_refill = 16; // finished lanes that trigger a refill (PT_PERSIST_REFILL)
-    // longest-first dispatch of the megakernel (PT_LPT=0 disables): cost[] / order[] of the last
-    // path-tracing draw, reused when the next draw has the same grid, target and program
-    bool lpt = true;
-    bool lpt_zig = false;     // PT_LPT=2: the order taken from both ends alternately (TraceArgs::order_zig)
-    bool zig_cont = true;     // (PT_LPT_ZIG_CONT) ... for compacting draws of up to lpt_flat_tiles tiles
-    bool xcd_blocked = false; // (experiment, PT_XCD_BLOCKED) without an order: a contiguous eighth of the tiles per XCD
-    unsigned prio_tiles = 0;   // longest-first: the first prio_tiles 16x16 tiles run at raised wave priority
-    unsigned split_tiles = 32; // longest-first: at most this many of the slowest tiles shaded by 16-lane waves
-                               // (pt_trace, pt_order_build; PT_SPLIT_TILES)
-    int split_near = 3;             // ... those within this many cost buckets of the slowest (1/8 octave each; PT_SPLIT_NEAR)
-    // (PT_LPT_FLAT, -1 = off) frames of more than 8192 tiles: the tiles more than this many buckets (1/8 octave
-    // each) below the slowest are dealt as one bucket, in about row-major order, so that the tiles in flight lie
-    // in one band of the frame (orderBuild). 6: dragon stand-in 4K +1.6-2.2 %, helmet 4K +8 %, sky + dragon 4K
-    // +0.9 %, bunny 4K ±0 (profiles/r06g_frames_lpt_flat_4k.log); 1080p frames keep the whole order
-    int lpt_flat = 6;
-    unsigned lpt_flat_tiles = 8192;   // (PT_LPT_FLAT_TILES) ... for frames of more than this many tiles
-    unsigned split_dominance = 8;   // ... when the slowest wave costs this many times the mean (PT_SPLIT_ALWAYS=1: 0)
-    // the order build of the last megakernel draw, deferred to run as an extra block of the next
-    // screenOutput pass (pt_output) instead of a kernel of its own; any other draw, stream switch or
-    // query launches it alone first (flush_order). PT_FUSE_ORDER=0: always alone, after the draw.
-    struct { bool on; unsigned n; const unsigned* cost; unsigned* order; unsigned* split; unsigned cap, dominance; int near; }
-        pending_order = {};
-    bool fuse_order = true;
-    // (PT_MAIN_WAVES) pt_blend / pt_output as up to this many one-wave workgroups (0: 4-wave blocks):
-    // beside overlapping path tracing a free wave slot comes one at a time, and a 4-wave workgroup waits
-    // for four on one CU (r05bi: dragon stand-in 1080p +2 %, helmet +3 %; at 4K -4 %, so only up to 8192
-    // tiles)
-    int main_waves = 16384;
-    size_t blend_1w_tiles = pt::kOrderHeld * 64u;   // (PT_BLEND_1W_TILES) pt_blend in one-wave form up to this many tiles
-    size_t out_1w_tiles = pt::kOrderHeld * 64u;     // (PT_OUT_1W_TILES) pt_output likewise, when no order build rides along
-    // (PT_ORDER_SIDE_TILES) frames of more tiles than this, drawn without lag, build their longest-first order
-    // as a one-wave block on their own side stream after the traced event, instead of riding along with the
-    // next screenOutput (which then needs no 4-wave block)
-    size_t order_side_tiles = ~(size_t)0;
+    // the order build of the last megakernel draw (longest-first dispatch: cost[] / order[] of a path-tracing
+    // draw, reused when the set's next draw has the same grid, target and program), deferred to run as an
+    // extra block of the next screenOutput pass (pt_output) instead of a kernel of its own; any other draw,
+    // stream switch or query launches it alone first (flush_order). k.fuse_order 0: always alone, after the draw.
+    bool order_pending = false;
+    pt::OrderArgs pending_order = {};
     unsigned* lpt_mem = nullptr;            // cost[kSetsMax][4 * cap] | order[kSetsMax][cap] | split[kSetsMax]
     size_t lpt_cap = 0;
     struct LptKey { bool valid; size_t n; const void* target; int prog, part, parts; };
@@ -257,10 +203,8 @@ struct Dev {
     unsigned* lpt_cost(int p) const { return lpt_mem + 4 * lpt_cap * p; }
     unsigned* lpt_order(int p) const { return lpt_mem + 4 * lpt_cap * kSetsMax + lpt_cap * p; }
     unsigned* lpt_split(int p) const { return lpt_mem + 5 * lpt_cap * kSetsMax + p; }
-    int sets() const { return depth + (lag >= 0 ? lag : kLagSmall); }   // buffer sets allocated (rad, compaction records)
-    // per-draw events for pt_last_render_ms: off until its first call (or PT_DRAW_EVENTS=1). Each
-    // hipEventRecord costs ~5 us of stream time between two kernels on MI355X (r02h: two pairs per
-    // frame were +19 us per frame, +1.7 % dragon stand-in, +3.8 % bunny)
+    int sets() const { return k.depth + (k.lag >= 0 ? k.lag : kLagSmall); }   // buffer sets allocated (rad, compaction records)
+    // per-draw events for pt_last_render_ms: off until its first call (or k.draw_events)
     bool draw_events = false;
     hipEvent_t ev0[kProgSlots] = {}, ev1[kProgSlots] = {};
     bool ev_used[kProgSlots] = {};
@@ -536,7 +480,7 @@ int spill_reserve(Dev* c, size_t lanes)
     if (lanes <= c->mk_spill_lanes) return PT_OK;
     if (c->mk_spill) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(c->mk_spill)); c->mk_spill = nullptr; }
     c->mk_spill_lanes = 0;
-    HIPCHK(c, hipMalloc(&c->mk_spill, (size_t)c->depth * lanes * kSpillPerLane * sizeof(float2)));
+    HIPCHK(c, hipMalloc(&c->mk_spill, (size_t)c->k.depth * lanes * kSpillPerLane * sizeof(float2)));
     c->mk_spill_lanes = lanes;
     c->need_fresh = true;   // new memory: the next draw waits for everything before it
     return PT_OK;
@@ -555,8 +499,8 @@ int rad_reserve(Dev* c, size_t pixels)
     return PT_OK;
 }
 
-// the overlap lag of a draw that traces `traced` pixels (Dev::lag)
-int draw_lag(const Dev* c, size_t traced) { return c->lag >= 0 ? c->lag : traced < c->lag_pixels ? Dev::kLagSmall : 0; }
+// the overlap lag of a draw that traces `traced` pixels (Knobs::lag)
+int draw_lag(const Dev* c, size_t traced) { return c->k.lag >= 0 ? c->k.lag : traced < (size_t)c->k.lag_pixels ? Dev::kLagSmall : 0; }
 
 // the pixels a draw of `target` traces: the owned 16-row bands of the partition (a bound on its records)
 size_t traced_pixels(const Dev* c, const DevTex* target)
@@ -576,7 +520,7 @@ size_t cont_bytes(const Dev* c, size_t paths)
 {
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     size_t per = paths * 64 + al(paths * 4) + 256;
-    if (c->cont_sort) per += 2 * al(paths * 4) + al(paths * 2) + pt::kSortBins * 4;
+    if (c->k.cont_sort) per += 2 * al(paths * 4) + al(paths * 2) + pt::kSortBins * 4;
     return per;
 }
 int cont_reserve(Dev* c, size_t paths, int sets)
@@ -609,26 +553,26 @@ void cont_args(Dev* c, int p, pt::TraceArgs& a)
     a.cont_rank = nullptr;
     a.cont_key = nullptr;
     a.cont_bins = nullptr;
-    a.cont_bounce = std::max(2u, c->cont_bounce);   // the G-buffer's normal / colour / id are final from bounce 2
-    a.cont_lanes = c->cont_lanes;
-    a.cont_refill = c->cont_refill;
+    a.cont_bounce = (unsigned)c->k.cont_bounce;   // (>= 2: the G-buffer's normal / colour / id are final from bounce 2)
+    a.cont_lanes = (unsigned)c->k.cont_lanes;
+    a.cont_refill = (unsigned)c->k.cont_refill;
 }
 
 // auto mode of late-bounce compaction (Dev::ContTune): whether this draw compacts
 int cont_decide_(Dev* c, const DevTex* target, int prog, bool eligible, bool* on, int* depth)
 {
     *on = false;
-    *depth = c->depth;
-    if (!eligible || c->cont_mode == 0) return PT_OK;
+    *depth = c->k.depth;
+    if (!eligible || c->k.cont_mode == 0) return PT_OK;
     // the records first, so that no trial block pays for their allocation (for every set the draws of this
-    // target cycle through: the depth, at most c->depth, plus the lag)
+    // target cycle through: the depth, at most k.depth, plus the lag)
     const size_t traced_approx = (size_t)target->w * target->h / (size_t)std::max(1, c->num_parts);   // (as render_trace's)
-    if (int rc = cont_reserve(c, traced_pixels(c, target), c->depth + draw_lag(c, traced_approx))) return rc;
-    if (c->cont_mode == 1) { *on = true; return PT_OK; }
+    if (int rc = cont_reserve(c, traced_pixels(c, target), c->k.depth + draw_lag(c, traced_approx))) return rc;
+    if (c->k.cont_mode == 1) { *on = true; return PT_OK; }
     auto& t = c->tune;
     if (t.target != target || t.prog != prog || t.part != c->part || t.parts != c->num_parts || t.w != target->w ||
         t.h != target->h)
-        t = Dev::ContTune{ target, prog, c->part, c->num_parts, target->w, target->h, 0, false, false, c->depth,
+        t = Dev::ContTune{ target, prog, c->part, c->num_parts, target->w, target->h, 0, false, false, c->k.depth,
                            0.0f, 0.0f, 0.0f };
     const int i = t.seen++ - Dev::kContSkip;
     if (t.decided) { *on = t.choice; *depth = t.depth; return PT_OK; }
@@ -642,11 +586,11 @@ int cont_decide_(Dev* c, const DevTex* target, int prog, bool eligible, bool* on
         // (the pixels this partition traces: a rank's bands of an N-GPU frame are a small frame -
         // r05ao: 0.5-1 Mpx frames lost 33-41 % to compaction)
         const size_t traced = (size_t)target->w * target->h / (size_t)std::max(1, c->num_parts);
-        *on = traced >= c->cont_auto_pixels || i >= -2;
+        *on = traced >= (size_t)c->k.cont_auto_pixels || i >= -2;
         // without compaction, frames of lag_pixels and more keep two frames in flight (r05aw: the
         // 4K frame's eighth at N = 8 +5.6 %; r05y: StanfordBunny 1080p +3.5 %), smaller ones three
         // and the lag (a 1920x136 frame: two lost a third, r05aa)
-        if (!*on && !c->depth_env && traced >= c->lag_pixels) *depth = std::min(2, c->depth);
+        if (!*on && !c->k.depth_env && traced >= (size_t)c->k.lag_pixels) *depth = std::min(2, c->k.depth);
         return PT_OK;
     }
     constexpr int B = Dev::kContBlock, S = Dev::kContSettle, M = Dev::kContMeasured, trial = Dev::kContBlocks * B;
@@ -663,7 +607,7 @@ int cont_decide_(Dev* c, const DevTex* target, int prog, bool eligible, bool* on
     }
     if (i < trial) {
         *on = b == 0 || b == Dev::kContBlocks - 1;   // on, off, off at depth 2 (twice), off, on
-        if (b == 2 || b == 3) *depth = std::min(2, c->depth);
+        if (b == 2 || b == 3) *depth = std::min(2, c->k.depth);
         return PT_OK;
     }
     // the trial's end: the host waits for it once (the draws it has already queued ran without), so that
@@ -680,7 +624,7 @@ int cont_decide_(Dev* c, const DevTex* target, int prog, bool eligible, bool* on
     t.decided = true;
     const bool two = t.ms_off2 < t.ms_off;
     t.choice = t.ms_on < 0.98f * std::min(t.ms_off, t.ms_off2);
-    t.depth = t.choice || !two ? c->depth : std::min(2, c->depth);
+    t.depth = t.choice || !two ? c->k.depth : std::min(2, c->k.depth);
     *on = t.choice;
     *depth = t.depth;
     return PT_OK;
@@ -691,8 +635,8 @@ int cont_decide(Dev* c, const DevTex* target, int prog, bool eligible, bool* on,
     int rc = cont_decide_(c, target, prog, eligible, on, depth);
     // what the draw did, for pt_queue_stats: 0 off, 1 auto decided off, 2 auto decided on, 3 forced on,
     // 4 auto trial
-    const bool tried = c->cont_mode == 2 && eligible;
-    c->cont_last = c->cont_mode == 1 && *on ? 3 : !tried ? 0 : c->tune.decided ? (c->tune.choice ? 2 : 1)
+    const bool tried = c->k.cont_mode == 2 && eligible;
+    c->cont_last = c->k.cont_mode == 1 && *on ? 3 : !tried ? 0 : c->tune.decided ? (c->tune.choice ? 2 : 1)
                  : c->tune.seen > Dev::kContSkip ? 4 : (*on ? 5 : 6);
     return rc;
 }
@@ -701,20 +645,9 @@ int cont_decide(Dev* c, const DevTex* target, int prog, bool eligible, bool* on,
 int overlap_init(Dev* c)
 {
     if (c->ts[0]) return PT_OK;
-    // (experiment, PT_SIDE_STREAMS=1) CU-masked side streams over every CU, each on a hardware queue of
-    // its own: with PT_OVERLAP_DEPTH=6, rank-sized dragon frames +30 %, the bunny's bimodal, 1080p -6 %
-    // (profiles/r05ad_*, r05an_*); stream priorities and CUs kept free for the main stream lost
-    const char* sk = std::getenv("PT_SIDE_STREAMS");
-    const int kind = sk ? std::atoi(sk) : 0;
     for (int p = 0; p < c->sets(); p++) HIPCHK(c, hipEventCreateWithFlags(&c->ev_mark[p], hipEventDisableTiming));
-    for (int p = 0; p < c->depth; p++) {
-        if (kind == 1) {
-            uint32_t mask[16];
-            for (auto& m : mask) m = 0xffffffffu;
-            HIPCHK(c, hipExtStreamCreateWithCUMask(&c->ts[p], 16, mask));
-        } else {
-            HIPCHK(c, hipStreamCreateWithFlags(&c->ts[p], hipStreamNonBlocking));
-        }
+    for (int p = 0; p < c->k.depth; p++) {
+        HIPCHK(c, hipStreamCreateWithFlags(&c->ts[p], hipStreamNonBlocking));
         HIPCHK(c, hipEventCreateWithFlags(&c->ev_traced[p], hipEventDisableTiming));
     }
     return PT_OK;
@@ -855,11 +788,9 @@ bool ensure_pairs(Dev* c, DevTex* t, const DevTex* tri, int* rc)
 // launch a deferred order build now, as its own kernel
 int flush_order(Dev* c)
 {
-    if (!c->pending_order.on) return PT_OK;
-    c->pending_order.on = false;
-    const auto& po = c->pending_order;
-    HIPCHK(c, pt_launch_order_build(po.n, po.cost, po.order, po.split, po.cap, po.dominance, po.near, c->stream,
-                                    1024));
+    if (!c->order_pending) return PT_OK;
+    c->order_pending = false;
+    HIPCHK(c, pt_launch_order_build(&c->pending_order, c->stream));
     return PT_OK;
 }
 
@@ -930,7 +861,7 @@ int render_trace(DevFx* fx, DevTex* target)
     {   // experiment builds: the wave timeline of the last megakernel draw (pt_debug_wave_log)
         static size_t cap = 0;
         const size_t tx = (size_t)((target->w + pt::kTile - 1) / pt::kTile);   // + split tiles' padding rows
-        const size_t need = (tx * bands_owned(c, target->h) * 4 + (4 * pt::kSplitParts - 4) * (size_t)c->split_tiles + 4 * tx) * pt::kWaveLogSlots;
+        const size_t need = (tx * bands_owned(c, target->h) * 4 + (4 * pt::kSplitParts - 4) * (size_t)c->k.split_tiles + 4 * tx) * pt::kWaveLogSlots;
         if (cap < need) { if (g_wave_log) hipFree(g_wave_log); hipMalloc(&g_wave_log, need * 8); cap = need; }
         hipMemsetAsync(g_wave_log, 0, need * 8, c->stream);   // padding workgroups leave zero rows
         g_wave_log_n = need / pt::kWaveLogSlots;
@@ -954,7 +885,7 @@ int render_trace(DevFx* fx, DevTex* target)
     if (c->backend == PT_BACKEND_PERSISTENT) {
         int rc = gb_reserve(c, (target->w + 1) & ~1, (target->h + 1) & ~1);
         if (rc) return rc;
-        const unsigned waves = (n_wave_tiles + c->persist_tiles - 1) / c->persist_tiles;
+        const unsigned waves = (n_wave_tiles + c->k.persist_tiles - 1) / c->k.persist_tiles;
         const size_t lanes = (size_t)((waves + 3) / 4) * pt::kBlock;
         if (lanes * kSpillPerLane > 0xffffffffull)   // 32-bit slab index
             return fail(c, PT_ERR_ARG, "render target too large for the BVH stack slab");
@@ -972,8 +903,8 @@ int render_trace(DevFx* fx, DevTex* target)
             HIPCHK(c, hipMemsetAsync(c->wf.cnt, 0, 16 * pt::kShards * sizeof(unsigned), c->stream));
             HIPCHK(c, pt_launch_wavefront(fx->prog, c->counting ? 1 : 0, &a, &c->wf, gx, gy, persist, c->stream));
         } else if (gy > 0) {
-            HIPCHK(c, pt_launch_persist(fx->prog, c->counting ? 1 : 0, &a, &c->gb, gx, n_wave_tiles, c->persist_tiles,
-                                        c->persist_refill, c->stream));
+            HIPCHK(c, pt_launch_persist(fx->prog, c->counting ? 1 : 0, &a, &c->gb, gx, n_wave_tiles, (unsigned)c->k.persist_tiles,
+                                        (unsigned)c->k.persist_refill, c->stream));
             HIPCHK(c, pt_launch_finish(&a, &c->gb, gx, gy, c->stream));
         }
         return end_draw(c, fx->prog);
@@ -984,12 +915,12 @@ int render_trace(DevFx* fx, DevTex* target)
     // tiles - their 16-lane waves would hand their slowest paths to pt_cont at once (r05j: dragon
     // stand-in 4K with both 2222 Mpaths/s, with compaction alone 2762)
     bool cont = false;
-    int depth = c->depth;
+    int depth = c->k.depth;
     if (int rc = cont_decide(c, target, fx->prog, mesh && !c->counting && !PT_SECPROF_BUILD, &cont, &depth)) return rc;
     // a moving-camera draw that runs alone (PT_MOVING_SERIAL) does not compact: with no next frame beside it,
     // pt_cont's tail (a wave waits for its longest chain of walks) is the frame's (dragon stand-in 1080p
     // 1.19 -> 1.09 ms per frame, profiles/r06af_movpx.log); its slowest tiles are split instead
-    if (a.moving && c->moving_serial) cont = false;
+    if (a.moving && c->k.moving_serial) cont = false;
     const size_t traced = (size_t)target->w * target->h / (size_t)std::max(1, c->num_parts);   // (about)
     const int lag = draw_lag(c, traced);
     if (depth != c->depth_run || lag != c->lag_run) {   // another buffer-set cycle: the draw waits for everything before it
@@ -1005,10 +936,11 @@ int render_trace(DevFx* fx, DevTex* target)
     // padding rows
     const size_t n = (size_t)gx * gy;   // 16x16 tiles
     const Dev::LptKey& key = c->lpt_key[par];
-    const bool lpt = c->lpt && !c->counting;
+    const bool lpt = c->k.lpt && !c->counting;
     const bool same = lpt && key.valid && key.n == n && key.target == target && key.prog == fx->prog &&
                       key.part == c->part && key.parts == c->num_parts && c->lpt_cap >= n;
-    const unsigned split = same && !cont ? (unsigned)std::min<size_t>(c->split_tiles, n) & ~7u : 0u;   // the cap
+    const unsigned split_cap = (unsigned)std::min<size_t>(c->k.split_tiles, n) & ~7u;
+    const unsigned split = same && !cont ? split_cap : 0u;
     const unsigned extra = 4u * pt::kSplitParts - 4u;   // more workgroups per split tile
     const int gy_grid = gy + (int)((extra * split + 4u * gx - 1) / (4u * gx));
     if (mesh) {
@@ -1027,7 +959,7 @@ int render_trace(DevFx* fx, DevTex* target)
         cont_args(c, par, a);
     }
     if (lpt && c->lpt_cap < n) {
-        if (c->lpt_mem) {   // (side-stream order builds write it after their traced event: every stream first)
+        if (c->lpt_mem) {   // (pt_trace on the side streams reads the order and writes the costs: every stream first)
             HIPCHK(c, hipStreamSynchronize(c->stream));
             for (int p = 0; p < Dev::kDepthMax; p++)
                 if (c->ts[p]) HIPCHK(c, hipStreamSynchronize(c->ts[p]));
@@ -1042,8 +974,8 @@ int render_trace(DevFx* fx, DevTex* target)
     // where the path tracing runs: a side stream gated by the main stream's state when the previous
     // megakernel draw began (or now: the first draw, after another schedule or a stream switch, with
     // counting kernels, or when a sampler is a render target, which draws on the main stream may write)
-    bool overlap = c->overlap && !c->counting && !PT_SECPROF_BUILD;   // (experiment builds: one wave log)
-    if (a.moving && c->moving_serial) overlap = false;
+    bool overlap = c->k.overlap && !c->counting && !PT_SECPROF_BUILD;   // (experiment builds: one wave log)
+    if (a.moving && c->k.moving_serial) overlap = false;
     for (const auto& kv : fx->samplers)
         if (kv.second && kv.second->kind == TEX_RT && kv.first != "previousBuffer") overlap = false;
     hipStream_t ts = c->stream;
@@ -1065,18 +997,16 @@ int render_trace(DevFx* fx, DevTex* target)
         if (!same) HIPCHK(c, hipMemsetAsync(c->lpt_cost(par), 0, 4 * n * sizeof(unsigned), ts));   // costs start afresh
         a.order = same ? c->lpt_order(par) : nullptr;
         a.cost = c->lpt_cost(par);
-        a.prio_tiles = a.order ? c->prio_tiles : 0u;
         // from both ends (runs of 8 tiles: the slowest, the cheapest, ...) also for compacting draws whose order
         // is not flattened: with the slowest tiles' late bounces handed to pt_cont, cheap tiles mixed in early
         // keep the slots full (dragon stand-in 1080p +1.5 %, its 20-frame run +1.7 %, helmet +1.6 %, three
         // rounds, profiles/r06bo_*; uncompacted the bunny lost 1.4 %, and at 4K the flattened order 1.9 %)
-        a.order_zig = c->lpt_zig || (cont && c->zig_cont && n <= c->lpt_flat_tiles) ? 1u : 0u;
+        a.order_zig = c->k.lpt_zig || (cont && c->k.zig_cont && n <= (size_t)c->k.lpt_flat_tiles) ? 1u : 0u;
         a.split = (a.order && split) ? c->lpt_split(par) : nullptr;
     }
     a.ntiles = (unsigned)n;
-    if (!a.order && c->xcd_blocked) a.order_zig = 2u;
     if (int rc = begin_draw(c, fx->prog, ts)) return rc;
-    if (cont && c->cont_sort && a.bvh_walk != pt::WALK_REF) {   // (the model's root box: child-pair walks only)
+    if (cont && c->k.cont_sort && a.bvh_walk != pt::WALK_REF) {   // (the model's root box: child-pair walks only)
         const size_t cap = c->cont_cap;
         auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
         char* m = (char*)a.cont_rec + cap * 64 + al(cap * 4);
@@ -1086,13 +1016,12 @@ int render_trace(DevFx* fx, DevTex* target)
         a.cont_bins = (unsigned*)(m + 2 * al(cap * 4) + al(cap * 2));
         // 8x8x8 cells for draws that trace 3 Mpx or more (4K: dragon stand-in +0.4 %, helmet +1.1 %, sky +
         // dragon +0.6 %, three rounds, profiles/r06bj_*; at 1080p the helmet lost 5.5 % with them, r06ao_*)
-        const unsigned gb = c->cont_grid_env || c->cont_key_mode >= 3u || traced < c->cont_big_pixels ? c->cont_grid_bits : 3u;
+        const unsigned gb = c->k.cont_grid_env || traced < (size_t)c->k.cont_big_pixels ? (unsigned)c->k.cont_grid_bits : 3u;
         for (int k = 0; k < 3; k++) {
             const float ext = a.bvh_root_box[3 + k] - a.bvh_root_box[k];
             a.cont_cell[k] = ext > 0.0f ? (float)(1u << gb) / ext : 0.0f;
         }
         a.cont_grid_bits = gb;
-        a.cont_key_mode = c->cont_key_mode;
     }
     HIPCHK(c, pt_launch_trace(fx->prog, c->counting ? 1 : 0, &a, gx, a.split ? gy_grid : gy, ts));
     if (a.cont_bins) {   // (PT_CONT_SORT) the records' order, from the keys' totals and ranks pt_trace took
@@ -1103,42 +1032,32 @@ int render_trace(DevFx* fx, DevTex* target)
         so.rank = a.cont_rank;
         so.bins = a.cont_bins;
         so.perm = (unsigned*)a.cont_perm;
-        so.chunk = c->sort_chunk;
-        so.nbins = (c->cont_key_mode == 3u ? 64u : c->cont_key_mode == 4u ? 32u : 16u) << (3u * a.cont_grid_bits);
+        so.nbins = 16u << (3u * a.cont_grid_bits);
         HIPCHK(c, pt_launch_cont_sort(&so, c->cont_cap, ts));
     }
     if (cont) {   // (its one-wave workgroups index the spill slab below the trace grid's lanes)
         // (the sky composite keeps 2048: its sky pixels store few records, and 1024 waves cost it 0.5 %)
-        const bool big = !c->cont_waves_env && traced >= c->cont_big_pixels && fx->prog != PT_PROG_SKY_MESH;
-        HIPCHK(c, pt_launch_cont(fx->prog, &a, (int)std::min<size_t>(big ? c->cont_waves_big : c->cont_waves, (size_t)gx * gy * 4), ts));
+        const bool big = !c->k.cont_waves_env && traced >= (size_t)c->k.cont_big_pixels && fx->prog != PT_PROG_SKY_MESH;
+        HIPCHK(c, pt_launch_cont(fx->prog, &a, (int)std::min<size_t>(big ? c->k.cont_waves_big : c->k.cont_waves, (size_t)gx * gy * 4), ts));
         c->cont_draws++;
     }
     // the draw's timing events bracket all of its path tracing on the side stream: pt_trace and, when the
     // draw compacts, pt_cont (the blend below is the main stream's)
     if (int rc = end_draw(c, fx->prog, ts)) return rc;
-    const int near_arg = c->split_near | ((c->lpt_flat + 1) << 8) | (int)((c->lpt_flat_tiles / 64u) << 16);
-    const unsigned split_cap = (unsigned)std::min<size_t>(c->split_tiles, n) & ~7u;
-    bool side_order = false;
     if (overlap) {
         HIPCHK(c, hipEventRecord(c->ev_traced[str], ts));
         HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_traced[str], 0));
-        // the set's next draw runs on this stream (no lag), so the order it reads is built by then
-        side_order = a.cost && lag == 0 && n > c->order_side_tiles;
-        if (side_order)
-            HIPCHK(c, pt_launch_order_build((unsigned)n, a.cost, c->lpt_order(par), c->lpt_split(par), split_cap,
-                                            c->split_dominance, near_arg, ts, 64));
     }
     // the history half of main() on the main stream, where the copy / output draws that read the
     // accumulation follow
     pt::BlendArgs b{ a.width, a.height, a.num_parts, a.part, a.frame, a.moving, a.rad, a.prev, a.out, a.cont_count, a.cont_bins };
     // (one-wave workgroups up to 8192 tiles, as the output pass below)
-    HIPCHK(c, pt_launch_blend(&b, gy, c->stream, n <= c->blend_1w_tiles ? c->main_waves : 0));
+    HIPCHK(c, pt_launch_blend(&b, gy, c->stream, n <= pt::kOrderHeld * 64u ? c->k.main_waves : 0));
     if (a.cost) {   // this draw's costs order draw k + 2: the build rides along with the next screenOutput
-        if (!side_order) {
-            c->pending_order = { true, (unsigned)n, a.cost, c->lpt_order(par), c->lpt_split(par), split_cap,
-                                 c->split_dominance, near_arg };
-            if (!c->fuse_order) { if (int rc = flush_order(c)) return rc; }
-        }
+        c->pending_order = { (unsigned)n, a.cost, c->lpt_order(par), c->lpt_split(par), split_cap,
+                             (unsigned)c->k.split_dominance, c->k.split_near, c->k.lpt_flat, (unsigned)c->k.lpt_flat_tiles };
+        c->order_pending = true;
+        if (!c->k.fuse_order) { if (int rc = flush_order(c)) return rc; }
         c->lpt_key[par] = { true, n, target, fx->prog, c->part, c->num_parts };
     }
     c->mk_seq++;
@@ -1199,12 +1118,8 @@ int render_output(DevFx* fx, DevTex* target)
     // frame size, same bands, and the copy target is not this pass's output
     const auto& pc = c->pending_copy;
     const int ow = target ? target->w : (c->cw || c->ch ? c->cw : acc->w), oh = target ? target->h : (c->cw || c->ch ? c->ch : acc->h);
-#ifdef PT_NO_FUSE_COPY   // experiment builds: the copy as its own kernel (what the fusion saves)
-    const bool fuse = false;
-#else
     const bool fuse = pc.on && pc.src == acc && pc.dst != target && ow == acc->w && oh == acc->h &&
                       pc.num_parts == a.num_parts && (pc.num_parts == 1 || pc.part == a.part);
-#endif
     if (fuse) { a.copy_dst = (float4*)pc.dst->d; c->pending_copy.on = false; }
     else { int frc = flush_copy(c); if (frc) return frc; }
     if (target) {
@@ -1219,24 +1134,21 @@ int render_output(DevFx* fx, DevTex* target)
     }
     // the order build rides along only up to 32768 tiles (4K): beyond, the block's 256 threads would
     // loop over memory and outlast the pass, so it runs alone first (1024 threads)
-    if (c->pending_order.on && c->pending_order.n > pt::kOrderHeld * 256u)
+    if (c->order_pending && c->pending_order.ntiles > pt::kOrderHeld * 256u)
         if (int frc = flush_order(c)) return frc;
     int rc = begin_draw(c, fx->prog);
     if (rc) return rc;
     if (a.width > 0 && a.height > 0) {
-        if (c->pending_order.on) {   // the last megakernel draw's order build rides along as one more block
-            const auto& po = c->pending_order;
-            a.ob_cost = po.cost; a.ob_order = po.order; a.ob_split = po.split;
-            a.ob_ntiles = po.n; a.ob_cap = po.cap; a.ob_dominance = po.dominance; a.ob_near = po.near;
-            c->pending_order.on = false;
+        if (c->order_pending) {   // the last megakernel draw's order build rides along as one more block
+            a.ob = c->pending_order;
+            c->order_pending = false;
         }
         // one-wave workgroups while a fused order build fits one wave's registers (<= 8192 tiles: up to
         // ~2 MP, and a rank's share of 4K), else the 4-wave blocks with a 256-thread order build
         const int nb = (a.height + 15) / 16, ob = a.part < nb ? (nb - a.part + a.num_parts - 1) / a.num_parts : 0;
         const unsigned tiles = (unsigned)((a.width + 15) / 16) * (unsigned)ob;   // (as pt_launch_output's grid)
-        const bool one = a.ob_cost ? tiles <= pt::kOrderHeld * 64u && a.ob_ntiles <= pt::kOrderHeld * 64u
-                                   : tiles <= c->out_1w_tiles;
-        HIPCHK(c, pt_launch_output(&a, c->stream, one ? c->main_waves : 0));
+        const bool one = std::max(tiles, a.ob.ntiles) <= pt::kOrderHeld * 64u;   // (ob.ntiles 0: no order build)
+        HIPCHK(c, pt_launch_output(&a, c->stream, one ? c->k.main_waves : 0));
     }
     return end_draw(c, fx->prog);
 }
@@ -1307,59 +1219,12 @@ Dev* dev_ctx_create(int device, int* err)
     auto* c = new Dev();
     c->device = device;
     c->cu_count = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    if (const char* v = std::getenv("PT_PERSIST_TILES")) c->persist_tiles = (unsigned)std::max(1, std::atoi(v));
-    if (const char* v = std::getenv("PT_DRAW_EVENTS")) c->draw_events = std::atoi(v) != 0;
-    if (const char* v = std::getenv("PT_LPT")) { c->lpt = std::atoi(v) != 0; c->lpt_zig = std::atoi(v) == 2; }
-    if (const char* v = std::getenv("PT_LPT_ZIG_CONT")) c->zig_cont = std::atoi(v) != 0;
-    if (const char* v = std::getenv("PT_XCD_BLOCKED")) c->xcd_blocked = std::atoi(v) != 0;
-    if (const char* v = std::getenv("PT_PRIO_TILES")) c->prio_tiles = (unsigned)std::max(0, std::atoi(v));
-    if (const char* v = std::getenv("PT_SPLIT_TILES")) c->split_tiles = (unsigned)std::max(0, std::atoi(v));
-    if (const char* v = std::getenv("PT_FUSE_ORDER")) c->fuse_order = std::atoi(v) != 0;
-    if (const char* v = std::getenv("PT_MAIN_WAVES")) c->main_waves = std::max(0, std::atoi(v));
-    if (const char* v = std::getenv("PT_BLEND_1W_TILES")) c->blend_1w_tiles = (size_t)std::max(0, std::atoi(v));
-    if (const char* v = std::getenv("PT_OUT_1W_TILES")) c->out_1w_tiles = (size_t)std::max(0, std::atoi(v));
-    if (const char* v = std::getenv("PT_ORDER_SIDE_TILES")) c->order_side_tiles = (size_t)std::max(0, std::atoi(v));
-    if (const char* v = std::getenv("PT_OVERLAP")) c->overlap = std::atoi(v) != 0;
-    if (const char* v = std::getenv("PT_MOVING_SERIAL")) c->moving_serial = std::atoi(v) != 0;
-    if (const char* v = std::getenv("PT_OVERLAP_DEPTH")) {
-        c->depth = std::min(Dev::kDepthMax, std::max(2, std::atoi(v)));
-        c->depth_env = true;
-    }
-    c->depth_run = c->depth;
-    if (const char* v = std::getenv("PT_OVERLAP_LAG")) c->lag = std::min(Dev::kLagMax, std::max(-1, std::atoi(v)));
-    if (const char* v = std::getenv("PT_OVERLAP_LAG_PIXELS")) c->lag_pixels = (size_t)std::max(0, std::atoi(v));
-    if (const char* v = std::getenv("PT_CONT")) c->cont_mode = std::min(2, std::max(0, std::atoi(v)));
-    if (const char* v = std::getenv("PT_CONT_BOUNCE")) c->cont_bounce = (unsigned)std::max(2, std::atoi(v));
-    if (const char* v = std::getenv("PT_CONT_LANES")) c->cont_lanes = (unsigned)std::min(64, std::max(1, std::atoi(v)));
-    if (const char* v = std::getenv("PT_CONT_REFILL")) c->cont_refill = (unsigned)std::min(64, std::max(1, std::atoi(v)));
-    if (const char* v = std::getenv("PT_CONT_SORT")) c->cont_sort = std::atoi(v) != 0;
-    if (const char* v = std::getenv("PT_CONT_SORT_CHUNK")) c->sort_chunk = (unsigned)std::max(64, std::atoi(v));
-    if (const char* v = std::getenv("PT_CONT_SORT_GRID")) { c->cont_grid_bits = (unsigned)std::min(3, std::max(1, std::atoi(v))); c->cont_grid_env = true; }
-    if (const char* v = std::getenv("PT_CONT_SORT_KEY")) c->cont_key_mode = (unsigned)std::min(4, std::max(0, std::atoi(v)));
-    if (c->cont_key_mode >= 3u) c->cont_grid_bits = std::min(2u, c->cont_grid_bits);   // (at most kSortBins keys)
-    if (const char* v = std::getenv("PT_CONT_WAVES")) { c->cont_waves = (unsigned)std::max(1, std::atoi(v)); c->cont_waves_env = true; }
-    if (const char* v = std::getenv("PT_CONT_WAVES_BIG")) c->cont_waves_big = (unsigned)std::max(1, std::atoi(v));
-    if (const char* v = std::getenv("PT_CONT_BIG_PIXELS")) c->cont_big_pixels = (size_t)std::max(0, std::atoi(v));
-    if (const char* v = std::getenv("PT_CONT_AUTO_PIXELS")) c->cont_auto_pixels = (size_t)std::max(0, std::atoi(v));
-    if (const char* v = std::getenv("PT_LPT_FLAT")) c->lpt_flat = std::max(-1, std::min(127, std::atoi(v)));
-    if (const char* v = std::getenv("PT_LPT_FLAT_TILES")) c->lpt_flat_tiles = (unsigned)std::max(0, std::min(1 << 21, std::atoi(v)));
-    if (const char* v = std::getenv("PT_SPLIT_NEAR")) c->split_near = std::max(1, std::min(128, std::atoi(v)));
-    if (const char* v = std::getenv("PT_SPLIT_ALWAYS")) c->split_dominance = std::atoi(v) ? 0u : 8u;
-    if (const char* v = std::getenv("PT_BVH_LAYOUT"))   // reference | pairs | trail: the context's initial walk
-        c->bvh_layout = !std::strcmp(v, "trail") ? PT_BVH_TRAIL : !std::strcmp(v, "reference") ? PT_BVH_REFERENCE
-                                                                                  : PT_BVH_PAIRS;
-    if (const char* v = std::getenv("PT_PERSIST_REFILL")) c->persist_refill = (unsigned)std::min(64, std::max(1, std::atoi(v)));
+    pt::read_knobs(c->k);
+    c->depth_run = c->k.depth;
+    c->bvh_layout = c->k.bvh_layout;
+    c->draw_events = c->k.draw_events != 0;
     hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) {
-        // (experiment, PT_MAIN_PRIO=1) the context's stream - blend, copy, output - at the device's highest
-        // priority, so that its small kernels take freed CU slots before the side streams' path tracing
-        const char* mp = std::getenv("PT_MAIN_PRIO");
-        int least = 0, greatest = 0;
-        if (mp && std::atoi(mp) != 0 && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess)
-            e = hipStreamCreateWithPriority(&c->own_stream, hipStreamNonBlocking, greatest);
-        else
-            e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking);
-    }
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking);
     c->stream = c->own_stream;
     if (e == hipSuccess) e = hipMalloc(&c->d_err, 256);
     if (e == hipSuccess) e = hipMalloc(&c->d_counters, pt::C_NUM * sizeof(unsigned long long));
@@ -1379,9 +1244,9 @@ void dev_ctx_destroy(Dev* c)
     if (!c) return;
     hipSetDevice(c->device);
     c->pending_copy.on = false;   // nothing can observe its target any more
-    c->pending_order.on = false;  // ... nor a next draw the order
+    c->order_pending = false;     // ... nor a next draw the order
     if (c->stream) hipStreamSynchronize(c->stream);
-    for (int p = 0; p < Dev::kDepthMax; p++)   // (side-stream order builds may still write the order arrays)
+    for (int p = 0; p < Dev::kDepthMax; p++)   // (pt_trace on the side streams reads and writes the order arrays)
         if (c->ts[p]) hipStreamSynchronize(c->ts[p]);
     std::vector<DevFx*> fx(c->effects.begin(), c->effects.end());
     for (auto* f : fx) dev_effect_destroy(f);
@@ -1712,7 +1577,7 @@ int dev_timing_begin(Dev* c)
     c->window = true;
     c->window_draws.clear();
     std::fill(c->window_seen, c->window_seen + kProgSlots, 0);
-    if (const char* v = std::getenv("PT_TIMING_EVERY")) c->timing_every = std::max(1, std::atoi(v));
+    c->timing_every = pt::knob_timing_every(c->timing_every);
     return PT_OK;
 }
 
@@ -1792,8 +1657,6 @@ int dev_queue_stats(Dev* c, uint32_t out[16])
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = flush_order(c)) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (int q = 0; q < Dev::kDepthMax; q++)   // (a side-stream order build may still write the split count)
-        if (c->ts[q]) HIPCHK(c, hipStreamSynchronize(c->ts[q]));
     const int p = (int)(c->mk_seq % (unsigned)(c->depth_run + c->lag_run));   // the tiles the next megakernel draw of the same grid splits
     if (c->lpt_mem && c->lpt_key[p].valid)
         HIPCHK(c, hipMemcpy(&out[7], c->lpt_split(p), sizeof(uint32_t), hipMemcpyDeviceToHost));

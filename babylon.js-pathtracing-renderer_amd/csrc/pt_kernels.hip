@@ -49,21 +49,19 @@ PT_D int costBucket(unsigned dur)
 // frame-to-frame noise of 64 random paths; measured 1-2 % better than the last frame alone) (one block): a tile weighs as its slowest quadrant wave; tiles are dealt
 // bucket by bucket, slowest bucket first; within a bucket the order is whatever the LDS atomics
 // give - any permutation renders the same bits, only the schedule changes.
-// (one block of 1024 threads as its own kernel, or of 256 as the extra block of pt_output)
-// near_arg: near_buckets (bits 0-7) | (flat + 1) << 8 (bits 8-15, 0 = no flattening) | the least tiles / 64 of a
-// flattened frame << 16: with flat >= 0, every
+// (one block of 1024 threads as its own kernel, or of 256 / 64 as the extra block of pt_output / pt_output_w)
+// Flattening (OrderArgs::flat >= 0, draws of more than flat_min tiles): every
 // bucket more than `flat` below the slowest tile's is dealt as one bucket, in (about) row-major order - the
 // slowest tiles still start first, the bulk of the frame sweeps down the screen, so the tiles in flight at
 // once lie in one band (their BVH working set shared in each XCD's L2)
-PT_D void orderBuild(unsigned ntiles, const unsigned* cost, unsigned* order, unsigned* split, unsigned split_cap,
-                     unsigned dominance, int near_arg)
+PT_D void orderBuild(const OrderArgs& a)
 {
+    const unsigned ntiles = a.ntiles;
+    const unsigned* const cost = a.cost;
     __shared__ unsigned cnt[kCostBuckets];
     __shared__ unsigned long long total;
     __shared__ unsigned slowest;
     __shared__ unsigned floorB;
-    const int near_buckets = near_arg & 255, flat = ((near_arg >> 8) & 255) - 1;
-    const unsigned flat_min = (unsigned)(near_arg >> 16) * 64u;   // flattening from this many tiles up
     for (int b = threadIdx.x; b < kCostBuckets; b += blockDim.x) cnt[b] = 0;
     if (threadIdx.x == 0) { total = 0; slowest = 0; }
     __syncthreads();
@@ -130,17 +128,17 @@ PT_D void orderBuild(unsigned ntiles, const unsigned* cost, unsigned* order, uns
             const int tl = 63 - __builtin_clzll(nz);
             top = 2 * tl + ((unsigned)__shfl((int)c1, tl, 64) != 0u ? 1 : 0);
         }
-        unsigned near = (2 * l <= top && 2 * l > top - near_buckets ? c0 : 0u) +
-                        (2 * l + 1 <= top && 2 * l + 1 > top - near_buckets ? c1 : 0u);
+        unsigned near = (2 * l <= top && 2 * l > top - a.near_buckets ? c0 : 0u) +
+                        (2 * l + 1 <= top && 2 * l + 1 > top - a.near_buckets ? c1 : 0u);
         for (int o = 1; o < 64; o <<= 1) near += (unsigned)__shfl_xor((int)near, o, 64);
-        const bool dominated = (unsigned long long)slowest * 4ull * ntiles >= dominance * total && total > 0;
+        const bool dominated = (unsigned long long)slowest * 4ull * ntiles >= a.dominance * total && total > 0;
         if (l == 0) {
             const unsigned k = (near + 7u) & ~7u;   // split_cap: a multiple of 8, <= ntiles
-            *split = dominated ? min(k, split_cap) : 0u;
+            *a.split = dominated ? min(k, a.split_cap) : 0u;
         }
         // flattening: the buckets below fl dealt as bucket fl (their counts folded into it) - for frames of more
         // than 8192 tiles (4K); at 1080p it lost on the helmet and StanfordBunny (-1.4 %, -2.5 %)
-        const int fl = flat >= 0 && ntiles > flat_min ? max(0, top - flat) : 0;
+        const int fl = a.flat >= 0 && ntiles > a.flat_min ? max(0, top - a.flat) : 0;
         unsigned below = (2 * l < fl ? c0 : 0u) + (2 * l + 1 < fl ? c1 : 0u);
         for (int o = 32; o > 0; o >>= 1) below += (unsigned)__shfl_xor((int)below, o, 64);
         unsigned f0 = 2 * l < fl ? 0u : c0, f1 = 2 * l + 1 < fl ? 0u : c1;
@@ -164,23 +162,18 @@ PT_D void orderBuild(unsigned ntiles, const unsigned* cost, unsigned* order, uns
             const unsigned t = threadIdx.x + j * blockDim.x;
             if (t < ntiles) {
                 const unsigned pos = atomicAdd(&cnt[max((bk[j >> 2] >> (8 * (j & 3))) & 255u, fb)], 1u);
-                if (pos < ntiles) order[pos] = t;
+                if (pos < ntiles) a.order[pos] = t;
             }
         }
         return;
     }
     for (unsigned t = threadIdx.x; t < ntiles; t += blockDim.x) {
         const unsigned pos = atomicAdd(&cnt[max((unsigned)tileBucket(t), fb)], 1u);
-        if (pos < ntiles) order[pos] = t;
+        if (pos < ntiles) a.order[pos] = t;
     }
 }
 
-__global__ __launch_bounds__(1024) void pt_order_build(unsigned ntiles, const unsigned* cost, unsigned* order,
-                                                        unsigned* split, unsigned split_cap, unsigned dominance,
-                                                        int near_buckets)
-{
-    orderBuild(ntiles, cost, order, split, split_cap, dominance, near_buckets);
-}
+__global__ __launch_bounds__(1024) void pt_order_build(OrderArgs a) { orderBuild(a); }
 // ------------------------------------------------------------------------------ screenCopy
 __global__ __launch_bounds__(256) void pt_copy(CopyArgs a)
 {
@@ -345,9 +338,9 @@ __global__ __launch_bounds__(256) void pt_output(OutputArgs a, int tiles_x, int 
         if (tid + 256 < 400) f1 = accAt(a, x0 + (tid + 256) % 20 - 2, y0 + (tid + 256) / 20 - 2);
     };
     int bid = (int)blockIdx.x, nblk = (int)gridDim.x;
-    if (a.ob_cost) {   // block 0: the next megakernel draw's order (pt_order_build), beside the tiles
+    if (a.ob.cost) {   // block 0: the next megakernel draw's order (pt_order_build), beside the tiles
         if (bid == 0) {
-            orderBuild(a.ob_ntiles, a.ob_cost, a.ob_order, a.ob_split, a.ob_cap, a.ob_dominance, a.ob_near);
+            orderBuild(a.ob);
             return;
         }
         bid--; nblk--;
@@ -402,9 +395,9 @@ __global__ __launch_bounds__(64) void pt_output_w(OutputArgs a, int tiles_x, int
         }
     };
     int bid = (int)blockIdx.x, nblk = (int)gridDim.x;
-    if (a.ob_cost) {   // block 0: the next megakernel draw's order (pt_order_build), beside the tiles
+    if (a.ob.cost) {   // block 0: the next megakernel draw's order (pt_order_build), beside the tiles
         if (bid == 0) {
-            orderBuild(a.ob_ntiles, a.ob_cost, a.ob_order, a.ob_split, a.ob_cap, a.ob_dominance, a.ob_near);
+            orderBuild(a.ob);
             return;
         }
         bid--; nblk--;
@@ -670,25 +663,23 @@ __global__ __launch_bounds__(64) void pt_cont_offsets(SortArgs s)
 }
 __global__ __launch_bounds__(64) void pt_cont_scatter(SortArgs s)
 {
-    const unsigned n = *s.count;
-    const unsigned begin = blockIdx.x * s.chunk, end = min(n, begin + s.chunk);
-    // eight records per lane at a time, their loads issued together (each record is a chain of three:
+    static_assert(kSortChunk == 8u * 64u, "a workgroup's records: eight per lane");
+    // eight records per lane, their loads issued together (each record is a chain of three:
     // key -> the key's first place -> the store)
-    for (unsigned i0 = begin + threadIdx.x; i0 < end; i0 += 8u * 64u) {
-        unsigned key[8], rank[8], at[8];
+    const unsigned i0 = blockIdx.x * kSortChunk + threadIdx.x, end = *s.count;
+    unsigned key[8], rank[8], at[8];
 #pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const unsigned i = i0 + 64u * k;
-            key[k] = i < end ? (unsigned)s.key[i] : 0u;
-            rank[k] = i < end ? s.rank[i] : 0u;
-        }
+    for (int k = 0; k < 8; k++) {
+        const unsigned i = i0 + 64u * k;
+        key[k] = i < end ? (unsigned)s.key[i] : 0u;
+        rank[k] = i < end ? s.rank[i] : 0u;
+    }
 #pragma unroll
-        for (int k = 0; k < 8; k++) at[k] = s.bins[key[k]];
+    for (int k = 0; k < 8; k++) at[k] = s.bins[key[k]];
 #pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const unsigned i = i0 + 64u * k;
-            if (i < end) s.perm[at[k] + rank[k]] = i;
-        }
+    for (int k = 0; k < 8; k++) {
+        const unsigned i = i0 + 64u * k;
+        if (i < end) s.perm[at[k] + rank[k]] = i;
     }
 }
 
@@ -739,17 +730,15 @@ hipError_t pt_launch_cont(int prog, const pt::TraceArgs* a, int waves, hipStream
 // (PT_CONT_SORT) the record order of a draw's pt_cont: up to `cap` records
 hipError_t pt_launch_cont_sort(const pt::SortArgs* a, size_t cap, hipStream_t s)
 {
-    const unsigned blocks = (unsigned)((cap + a->chunk - 1) / a->chunk);
+    const unsigned blocks = (unsigned)((cap + pt::kSortChunk - 1) / pt::kSortChunk);
     hipLaunchKernelGGL(pt::pt_cont_offsets, dim3(1), dim3(64), 0, s, *a);
     hipLaunchKernelGGL(pt::pt_cont_scatter, dim3(blocks ? blocks : 1), dim3(64), 0, s, *a);
     return hipGetLastError();
 }
 
-hipError_t pt_launch_order_build(unsigned ntiles, const unsigned* cost, unsigned* order, unsigned* split,
-                                 unsigned split_cap, unsigned dominance, int near_buckets, hipStream_t s, int threads)
+hipError_t pt_launch_order_build(const pt::OrderArgs* a, hipStream_t s)
 {
-    hipLaunchKernelGGL(pt::pt_order_build, dim3(1), dim3(threads), 0, s, ntiles, cost, order, split, split_cap, dominance,
-                       near_buckets);
+    hipLaunchKernelGGL(pt::pt_order_build, dim3(1), dim3(1024), 0, s, *a);
     return hipGetLastError();
 }
 
@@ -825,25 +814,19 @@ hipError_t pt_launch_output(const pt::OutputArgs* a, hipStream_t s, int waves)
     const int nb = (a->height + 15) / 16;
     dim3 grid((a->width + 15) / 16, a->part < nb ? (nb - a->part + a->num_parts - 1) / a->num_parts : 0);
     if (grid.y == 0) {   // no band of this part: a fused order build runs on its own
-        if (a->ob_cost)
-            hipLaunchKernelGGL(pt::pt_order_build, dim3(1), dim3(1024), 0, s, a->ob_ntiles, a->ob_cost, a->ob_order,
-                               a->ob_split, a->ob_cap, a->ob_dominance, a->ob_near);
+        if (a->ob.cost) return pt_launch_order_build(&a->ob, s);
         return hipGetLastError();
     }
     // persistent screenOutput blocks: about four 16x16 tiles each, 4096..8192 (1080p 4096: 37.2 ->
-    // 36.1 us; 4K 8192: 122 -> 109 us; profiles/r02i_ab_out_blocks.txt); PT_OUT_BLOCKS fixes the count
+    // 36.1 us; 4K 8192: 122 -> 109 us; profiles/r02i_ab_out_blocks.txt)
     const int ntiles = (int)(grid.x * grid.y);
     if (waves > 0) {
-        hipLaunchKernelGGL(pt::pt_output_w, dim3((ntiles < waves ? ntiles : waves) + (a->ob_cost ? 1 : 0)), dim3(64), 0, s,
+        hipLaunchKernelGGL(pt::pt_output_w, dim3((ntiles < waves ? ntiles : waves) + (a->ob.cost ? 1 : 0)), dim3(64), 0, s,
                            *a, (int)grid.x, ntiles);
         return hipGetLastError();
     }
-#ifdef PT_OUT_BLOCKS
-    const int blocks = PT_OUT_BLOCKS;
-#else
     const int blocks = ntiles / 4 < 4096 ? 4096 : ntiles / 4 > 8192 ? 8192 : ntiles / 4;
-#endif
-    hipLaunchKernelGGL(pt::pt_output, dim3((ntiles < blocks ? ntiles : blocks) + (a->ob_cost ? 1 : 0)), dim3(256), 0, s, *a,
+    hipLaunchKernelGGL(pt::pt_output, dim3((ntiles < blocks ? ntiles : blocks) + (a->ob.cost ? 1 : 0)), dim3(256), 0, s, *a,
                        (int)grid.x, ntiles);
     return hipGetLastError();
 }

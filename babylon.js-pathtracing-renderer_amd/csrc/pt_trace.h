@@ -240,7 +240,7 @@ struct GBits {
     }
 };
 
-// (experiment, PT_CONT_SORT) a stored record's ray key - whether the ray samples the light (the any-hit
+// (PT_CONT_SORT, on by default) a stored record's ray key - whether the ray samples the light (the any-hit
 // walk), the origin's cell in a 4x4x4 grid over the model's box (Morton order), the direction's octant -
 // and its rank among the key's records: the lanes of one key found by a ballot per distinct key, then one
 // atomic per key (all in one instruction) on the key's total. pt_cont_scatter places the records by them.
@@ -259,19 +259,7 @@ PT_D void contRank(const TraceArgs& a, int slot, const Path& p, const PState& s,
         const unsigned cell = spread(cx) | (spread(cy) << 1) | (spread(cz) << 2);
         const unsigned oct = (p.rd.x < 0.0f ? 1u : 0u) | (p.rd.y < 0.0f ? 2u : 0u) | (p.rd.z < 0.0f ? 4u : 0u);
         const unsigned lt = s.sampleLight ? 1u : 0u;
-        if (a.cont_key_mode == 3u) {   // 24 directions: the major axis and its sign (cube face), the quadrant
-            const float ax = fabsf(p.rd.x), ay = fabsf(p.rd.y), az = fabsf(p.rd.z);
-            const unsigned face = ax >= ay && ax >= az ? 0u : ay >= az ? 1u : 2u;
-            const float m = face == 0u ? p.rd.x : face == 1u ? p.rd.y : p.rd.z;
-            const float u = face == 0u ? p.rd.y : p.rd.x, v = face == 2u ? p.rd.y : p.rd.z;
-            const unsigned dir = ((face * 2u + (m < 0.0f ? 1u : 0u)) << 2) | (u < 0.0f ? 1u : 0u) | (v < 0.0f ? 2u : 0u);
-            key = (lt << (5u + 3u * gb)) | (cell << 5) | dir;
-        } else
-        key = a.cont_key_mode == 1u ? (lt << (3u + 3u * gb)) | (oct << (3u * gb)) | cell   // octant-major
-            : a.cont_key_mode == 2u ? (cell << 3) | oct                                   // no light flag
-            : a.cont_key_mode == 4u   // the paths with more bounces left first (longest first), then as mode 0
-                ? (lt << (4u + 3u * gb)) | (((unsigned)s.bounce > a.cont_bounce ? 1u : 0u) << (3u + 3u * gb)) | (cell << 3) | oct
-            : (lt << (3u + 3u * gb)) | (cell << 3) | oct;
+        key = (lt << (3u + 3u * gb)) | (cell << 3) | oct;
     }
     unsigned long long todo = __ballot(inside), peers = 0ull;
     while (todo) {   // (wave-uniform)
@@ -391,15 +379,11 @@ PT_D bool tracePlace(const TraceArgs& a, int lane, TracePlace& pl)
         wave = (int)(r / T);
     }
     unsigned rank = slot;   // the slot's place in the longest-first order
-    if (a.order_zig == 1u && slot >= K) {   // runs of 8 (one tile per XCD): from the top and the bottom in turn
+    if (a.order_zig && slot >= K) {   // runs of 8 (one tile per XCD): from the top and the bottom in turn
         const unsigned j = slot - K, m = ntiles - K, g = j >> 3, t = (g >> 1) * 8u + (j & 7u);
         rank = K + ((g & 1u) ? m - 1u - t : t);
     }
-    // (experiment, PT_XCD_BLOCKED with PT_LPT=0: XCD j = slot % 8 takes the j-th eighth of the frame's tiles in
-    // row-major order - each L2 sees one contiguous strip of the frame, whatever its cost)
-    const unsigned tile = a.order ? a.order[rank]
-                                  : (a.order_zig == 2u && (ntiles & 7u) == 0u) ? (slot & 7u) * (ntiles >> 3) + (slot >> 3) : slot;
-    if (rank < a.prio_tiles) __builtin_amdgcn_s_setprio(3);   // the critical path: issue first
+    const unsigned tile = a.order ? a.order[rank] : slot;
     const int tx = (int)(tile % tiles_x);
     const unsigned bY = tile / tiles_x;
     // lane bits (x0, y0, x1, x2, y1, y2) of an 8x8 block, or (x0, y0, x1, y1) of a split tile's 4x4

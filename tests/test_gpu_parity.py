@@ -329,21 +329,20 @@ def test_overlapped_frames_observed_between_draws(engine, size):
 
 
 @pytest.mark.parametrize("layout,order", [("pairs", "keys"), ("trail", "keys"), ("pairs", "stored"),
-                                          ("pairs", "octant-major 8x8x8")])
+                                          ("pairs", "keys 8x8x8")])
 def test_late_bounce_compaction_1080p_bitexact(monkeypatch, layout, order):
     """Late-bounce compaction forced on (PT_CONT=1, from bounce 2 for waves with <= 48 live paths, the
     default PT_CONT_LANES: the
     pt_trace<P,false,true> variant stores them, pt_cont runs them packed on the draw's side stream):
     the dragon stand-in's four recorded 1920x1080 frames, accumulation and canvas bit-exact - with pt_cont
     taking the records in ray-key order (the default: 4x4x4 cells, light flag first), in store order
-    (PT_CONT_SORT=0), and in the 8192-key octant-major order (PT_CONT_SORT_GRID=3, PT_CONT_SORT_KEY=1)."""
+    (PT_CONT_SORT=0), and in the 8192-key order of 8x8x8 cells that 4K draws take (PT_CONT_SORT_GRID=3)."""
     import babylon_pt as bp
     monkeypatch.setenv("PT_CONT", "1")
     if order == "stored":
         monkeypatch.setenv("PT_CONT_SORT", "0")
     elif order != "keys":
         monkeypatch.setenv("PT_CONT_SORT_GRID", "3")
-        monkeypatch.setenv("PT_CONT_SORT_KEY", "1")
     e = bp.Engine(0)
     try:
         e.set_bvh_layout(layout)
@@ -398,6 +397,80 @@ def test_late_bounce_compaction_auto_mode_bitexact(monkeypatch):
     assert qs["late_bounce_compaction"] in ("auto: on", "auto: off"), qs
     assert qs["frames_in_flight"] == 3 if qs["late_bounce_compaction"] == "auto: on" else qs["frames_in_flight"] in (2, 3)
     assert qs["compaction_trial_ratio"] and 0.2 < qs["compaction_trial_ratio"] < 5.0, qs
+
+
+_KNOB_REF = {}
+
+
+def _schedule_knobs_reference(player, meta, mesh, W, Hh):
+    """The 12 frames of test_schedule_knobs_bitexact and the oracle's last accumulation and canvas of them:
+    the same for every case, so computed once."""
+    if not _KNOB_REF:
+        frames = meta["frames"] + [player.synth_frame(k) for k in range(8)]
+        ref_acc, ref_can, _ = H.oracle_replay(dict(meta, frames=frames), None, W, Hh, with_output=True, mesh=mesh)
+        _KNOB_REF.update(frames=frames, acc=ref_acc[-1], can=ref_can[-1])
+    return _KNOB_REF
+
+
+_CONT_ON = {"PT_CONT": "1"}
+_SCHEDULE_KNOBS = {
+    # longest-first order flattened below the slowest buckets, at a threshold this frame's 510 tiles exceed ...
+    "flat": dict(_CONT_ON, PT_LPT_FLAT_TILES="64", PT_LPT_FLAT="2"),
+    # ... and at one that is no multiple of 64 (host and kernel compare the tiles with the same number)
+    "flat-odd": dict(_CONT_ON, PT_LPT_FLAT_TILES="100", PT_LPT_FLAT="2"),
+    "zig": {"PT_LPT": "2"},                      # the order from both ends, every draw
+    "zig-cont-off": dict(_CONT_ON, PT_LPT_ZIG_CONT="0"),   # compacting draws in the plain order
+    "order-alone": {"PT_FUSE_ORDER": "0"},       # the order build as its own kernel after each draw
+    "four-wave-main": {"PT_MAIN_WAVES": "0"},    # pt_blend / pt_output as 4-wave blocks
+    "serial": {"PT_OVERLAP": "0"},               # every draw on the context's stream
+    "depth2-cont": dict(_CONT_ON, PT_OVERLAP_DEPTH="2", PT_CONT_WAVES="64", PT_CONT_REFILL="8", PT_CONT_BOUNCE="3"),
+    "moving-overlapped": {"PT_MOVING_SERIAL": "0"},
+    "split-near": {"PT_SPLIT_ALWAYS": "1", "PT_SPLIT_TILES": "64", "PT_SPLIT_NEAR": "8"},
+    "persist": {"PT_PERSIST_TILES": "2", "PT_PERSIST_REFILL": "8"},   # (the persistent backend)
+}
+
+
+@pytest.mark.parametrize("case", list(_SCHEDULE_KNOBS))
+def test_schedule_knobs_bitexact(monkeypatch, case):
+    """The schedule knobs that are not defaults (INTEGRATION.md's table) change when and where a pixel is
+    computed, never its value. The dragon stand-in at 480x272 - 30 x 17 = 510 tiles, no multiple of 8, so the
+    short last run of the tile placement and of the both-ends order is taken - over the four recorded
+    frames and eight still-camera ones, issued with no sync between them: the last accumulation and canvas
+    equal the oracle's bits under each setting. No overlap lag in any case, so that a buffer set, and with
+    it an order built from its costs, comes round again within the 12 draws."""
+    import copy
+    import babylon_pt as bp
+    W, Hh = 480, 272
+    assert ((W + 15) // 16) * ((Hh + 15) // 16) == 510
+    monkeypatch.setenv("PT_OVERLAP_LAG", "0")
+    for name, value in _SCHEDULE_KNOBS[case].items():
+        monkeypatch.setenv(name, value)
+    e = bp.Engine(0)
+    try:
+        if case == "persist":
+            e.set_backend("persistent")
+        meta = copy.deepcopy(H.stream("gltf_bunny_1080p"))
+        mesh = _dragon()
+        player = bp.StreamPlayer(e, meta, H.bluenoise(), H.texture_payloads(meta, mesh), W, Hh)
+        ref = _schedule_knobs_reference(player, meta, mesh, W, Hh)
+        e.resize_canvas(W, Hh)
+        for calls in ref["frames"]:
+            for call in calls:
+                player.play_call(call)
+        e.sync()
+        qs = e.queue_stats()   # (of the last draw; the split count is what the next draw of its buffer set takes)
+        got_acc = player.textures["pathTracingRenderTarget"].read()
+        got_can = e.read_canvas(W, Hh)
+    finally:
+        e.dispose()
+    assert _bits_equal(ref["acc"], got_acc), "%s: %s" % (case, _diff_report(ref["acc"], got_acc))
+    assert _bits_equal(ref["can"], got_can), "%s canvas: %s" % (case, _diff_report(ref["can"], got_can))
+    if "PT_CONT" in _SCHEDULE_KNOBS[case]:
+        assert qs["late_bounce_compaction"] == "on", qs
+    if case == "depth2-cont":
+        assert qs["frames_in_flight"] == 2, qs
+    if case == "split-near":
+        assert qs["split_tiles"] >= 8, qs
 
 
 def _oracle_at(meta, frames, W, Hh, mesh, keep_acc, keep_can):
