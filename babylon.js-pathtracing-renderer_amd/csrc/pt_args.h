@@ -251,7 +251,8 @@ struct BlendArgs {
     const float4* rad;
     const float4* prev;
     float4* out;
-    unsigned* cont_count;   // late-bounce compaction: the draw's record counter, zeroed here (NULL: none)
+    unsigned* cont_count;   // late-bounce compaction: the draw's record counter, added to the buffer set's 64-bit
+                            // total at [2..3] (pt_cont_stats) and zeroed here (NULL: none)
     unsigned* cont_bins;    // (PT_CONT_SORT) the record sort's kSortBins totals, zeroed here (NULL: none)
 };
 

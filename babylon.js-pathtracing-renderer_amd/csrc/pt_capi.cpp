@@ -164,6 +164,7 @@ struct Dev {
     void* cont_mem = nullptr;
     size_t cont_cap = 0;          // records per buffer set ...
     int cont_sets = 0;            // ... and buffer sets allocated
+    uint64_t cont_stored = 0;     // records stored by draws of earlier allocations (pt_cont_stats; cont_reserve)
     // auto mode: compaction pays on the heavy 4K frames (sky + dragon +19 %, dragon stand-in +10 %) and
     // costs elsewhere (bunny 4K -22 %, helmet -9 %, rank-sized frames -29 %: profiles/r05i_*), which
     // the draw's arguments do not tell apart. So the draws of one target / program / partition time it:
@@ -523,12 +524,33 @@ size_t cont_bytes(const Dev* c, size_t paths)
     if (c->k.cont_sort) per += 2 * al(paths * 4) + al(paths * 2) + pt::kSortBins * 4;
     return per;
 }
+// the records the draws of the current allocation stored: the buffer sets' running totals, which each draw's
+// pt_blend keeps in its counter block (the main stream must be idle)
+int cont_totals(Dev* c, uint64_t* sum)
+{
+    *sum = 0;
+    const size_t per = cont_bytes(c, c->cont_cap);
+    for (int p = 0; c->cont_mem && p < c->cont_sets; p++) {
+        uint64_t v = 0;
+        HIPCHK(c, hipMemcpy(&v, (char*)c->cont_mem + (size_t)(p + 1) * per - 256 + 2 * sizeof(unsigned), sizeof(v),
+                            hipMemcpyDeviceToHost));
+        *sum += v;
+    }
+    return PT_OK;
+}
 int cont_reserve(Dev* c, size_t paths, int sets)
 {
     if (paths <= c->cont_cap && sets <= c->cont_sets) return PT_OK;
     paths = std::max(paths, c->cont_cap);
     sets = std::max(sets, c->cont_sets);
-    if (c->cont_mem) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(c->cont_mem)); c->cont_mem = nullptr; }
+    if (c->cont_mem) {   // (the totals of the sets that go are carried over on the host)
+        uint64_t stored = 0;
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (int rc = cont_totals(c, &stored)) return rc;
+        c->cont_stored += stored;
+        HIPCHK(c, hipFree(c->cont_mem));
+        c->cont_mem = nullptr;
+    }
     c->cont_cap = 0;
     c->cont_sets = 0;
     const size_t per = cont_bytes(c, paths);
@@ -558,8 +580,10 @@ void cont_args(Dev* c, int p, pt::TraceArgs& a)
     a.cont_refill = (unsigned)c->k.cont_refill;
 }
 
-// auto mode of late-bounce compaction (Dev::ContTune): whether this draw compacts
-int cont_decide_(Dev* c, const DevTex* target, int prog, bool eligible, bool* on, int* depth)
+// auto mode of late-bounce compaction (Dev::ContTune): whether this draw compacts. `alone`: a moving-camera
+// draw that runs alone and never compacts (render_trace) is no draw of the trial - it leaves the tune as it
+// is (not counted, no event) and only takes the frames in flight a still draw in its place would
+int cont_decide_(Dev* c, const DevTex* target, int prog, bool eligible, bool alone, bool* on, int* depth)
 {
     *on = false;
     *depth = c->k.depth;
@@ -570,12 +594,15 @@ int cont_decide_(Dev* c, const DevTex* target, int prog, bool eligible, bool* on
     if (int rc = cont_reserve(c, traced_pixels(c, target), c->k.depth + draw_lag(c, traced_approx))) return rc;
     if (c->k.cont_mode == 1) { *on = true; return PT_OK; }
     auto& t = c->tune;
-    if (t.target != target || t.prog != prog || t.part != c->part || t.parts != c->num_parts || t.w != target->w ||
-        t.h != target->h)
+    bool same = t.target == target && t.prog == prog && t.part == c->part && t.parts == c->num_parts && t.w == target->w &&
+                t.h == target->h;
+    if (!same && !alone) {
         t = Dev::ContTune{ target, prog, c->part, c->num_parts, target->w, target->h, 0, false, false, c->k.depth,
                            0.0f, 0.0f, 0.0f };
-    const int i = t.seen++ - Dev::kContSkip;
-    if (t.decided) { *on = t.choice; *depth = t.depth; return PT_OK; }
+        same = true;
+    }
+    const int i = (alone ? (same ? t.seen : 0) : t.seen++) - Dev::kContSkip;
+    if (same && t.decided) { *on = t.choice; *depth = t.depth; return PT_OK; }
     // before the trial, the default: on for frames of at least cont_auto_pixels (with three frames in
     // flight it won on every frame of 2 MP and more but the light bunny, and lost on the rank-sized one,
     // profiles/r05q_frames_depth_x_compaction.txt); the two draws before the trial compact, one per side
@@ -600,7 +627,7 @@ int cont_decide_(Dev* c, const DevTex* target, int prog, bool eligible, bool* on
     // longest-first order came from the other mode's costs) and the block's last B - S - M draws keep the
     // next block's frames out of the timed ones.
     const int b = i / B, o = i % B;
-    if (i < trial && (o == S || o == S + M)) {
+    if (i < trial && (o == S || o == S + M) && !alone) {
         hipEvent_t& e = c->tune_ev[2 * b + (o == S ? 0 : 1)];
         if (!e) HIPCHK(c, hipEventCreate(&e));
         HIPCHK(c, hipEventRecord(e, c->stream));
@@ -610,6 +637,7 @@ int cont_decide_(Dev* c, const DevTex* target, int prog, bool eligible, bool* on
         if (b == 2 || b == 3) *depth = std::min(2, c->k.depth);
         return PT_OK;
     }
+    if (alone) return PT_OK;   // (the next still draw ends the trial)
     // the trial's end: the host waits for it once (the draws it has already queued ran without), so that
     // every later draw of this target takes the decision; the faster block of each mode decides (one
     // stray block cannot)
@@ -630,12 +658,13 @@ int cont_decide_(Dev* c, const DevTex* target, int prog, bool eligible, bool* on
     return PT_OK;
 }
 
-int cont_decide(Dev* c, const DevTex* target, int prog, bool eligible, bool* on, int* depth)
+int cont_decide(Dev* c, const DevTex* target, int prog, bool eligible, bool alone, bool* on, int* depth)
 {
-    int rc = cont_decide_(c, target, prog, eligible, on, depth);
+    int rc = cont_decide_(c, target, prog, eligible, alone, on, depth);
+    if (alone) *on = false;
     // what the draw did, for pt_queue_stats: 0 off, 1 auto decided off, 2 auto decided on, 3 forced on,
     // 4 auto trial
-    const bool tried = c->k.cont_mode == 2 && eligible;
+    const bool tried = c->k.cont_mode == 2 && eligible && !alone;
     c->cont_last = c->k.cont_mode == 1 && *on ? 3 : !tried ? 0 : c->tune.decided ? (c->tune.choice ? 2 : 1)
                  : c->tune.seen > Dev::kContSkip ? 4 : (*on ? 5 : 6);
     return rc;
@@ -916,11 +945,12 @@ int render_trace(DevFx* fx, DevTex* target)
     // stand-in 4K with both 2222 Mpaths/s, with compaction alone 2762)
     bool cont = false;
     int depth = c->k.depth;
-    if (int rc = cont_decide(c, target, fx->prog, mesh && !c->counting && !PT_SECPROF_BUILD, &cont, &depth)) return rc;
     // a moving-camera draw that runs alone (PT_MOVING_SERIAL) does not compact: with no next frame beside it,
     // pt_cont's tail (a wave waits for its longest chain of walks) is the frame's (dragon stand-in 1080p
-    // 1.19 -> 1.09 ms per frame, profiles/r06af_movpx.log); its slowest tiles are split instead
-    if (a.moving && c->k.moving_serial) cont = false;
+    // 1.19 -> 1.09 ms per frame, profiles/r06af_movpx.log); its slowest tiles are split instead. Nor is it a
+    // draw of the auto trial, and pt_queue_stats reports it as not compacting.
+    const bool alone = a.moving && c->k.moving_serial;
+    if (int rc = cont_decide(c, target, fx->prog, mesh && !c->counting && !PT_SECPROF_BUILD, alone, &cont, &depth)) return rc;
     const size_t traced = (size_t)target->w * target->h / (size_t)std::max(1, c->num_parts);   // (about)
     const int lag = draw_lag(c, traced);
     if (depth != c->depth_run || lag != c->lag_run) {   // another buffer-set cycle: the draw waits for everything before it
@@ -1675,6 +1705,19 @@ int dev_queue_stats(Dev* c, uint32_t out[16])
             out[b] += h[b * pt::kShards + s];
             if (b < 6) out[8 + b] += h[(8 + b) * pt::kShards + s];
         }
+    return PT_OK;
+}
+
+int dev_cont_stats(Dev* c, uint64_t out[2])
+{
+    if (!c || !out) return PT_ERR_ARG;
+    out[0] = out[1] = 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // (every draw's pt_blend, which keeps the totals, is on it)
+    uint64_t stored = 0;
+    if (int rc = cont_totals(c, &stored)) return rc;
+    out[0] = c->cont_stored + stored;
+    out[1] = c->cont_draws;
     return PT_OK;
 }
 

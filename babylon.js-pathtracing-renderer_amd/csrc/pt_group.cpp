@@ -700,6 +700,19 @@ int pt_queue_stats(pt_ctx* c, uint32_t out[16])
     return PT_OK;
 }
 
+int pt_cont_stats(pt_ctx* c, uint64_t out[2])
+{
+    if (!c || !out) return PT_ERR_ARG;
+    out[0] = out[1] = 0;
+    for (int k = 0; k < c->n(); k++) {
+        uint64_t v[2];
+        if (int rc = take(c, k, dev_cont_stats(c->parts[k], v))) return rc;
+        out[0] += v[0];
+        out[1] += v[1];
+    }
+    return PT_OK;
+}
+
 int pt_math_probe(pt_ctx* c, int op, const float* x, const float* y, float* out, int n)
 {
     if (!c) return PT_ERR_ARG;

@@ -225,12 +225,20 @@ PT_D void blendRows(const BlendArgs& a, int x, int r0)
         a.out[(long long)y * a.width + x] = make_float4(prev.x + cr, prev.y + cg, prev.z + cb, ca);
     }
 }
+// The draw's record counter and pt_cont's queue head (threads 0 and 1 of the first workgroup; pt_cont is
+// done), zeroed for the buffer set's next draw. Thread 0 first adds the count to the set's running total
+// (pt_cont_stats), 64 bits at cont_count[2..3]: one writer per buffer set, ordered by the stream.
+PT_D void contCountReset(unsigned* cc)
+{
+    if (threadIdx.x == 0) *(unsigned long long*)(cc + 2) += cc[0];
+    cc[threadIdx.x] = 0u;
+}
 __global__ __launch_bounds__(256) void pt_blend(BlendArgs a)
 {
     const int band = blockIdx.y * a.num_parts + a.part;
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);
     const int r0 = band * kTile + (threadIdx.x >> 6);
-    if (a.cont_count && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 2) a.cont_count[threadIdx.x] = 0u;   // counter, queue head (pt_cont is done)
+    if (a.cont_count && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 2) contCountReset(a.cont_count);
     if (a.cont_bins && blockIdx.x == 0 && blockIdx.y == 0)
         for (int i = threadIdx.x; i < kSortBins; i += 256) a.cont_bins[i] = 0u;
     if (x >= a.width) return;
@@ -241,7 +249,7 @@ __global__ __launch_bounds__(256) void pt_blend(BlendArgs a)
 // for four on one CU (the main stream's small kernels then took 100-600 us)
 __global__ __launch_bounds__(64) void pt_blend_w(BlendArgs a, int units_x, int units)
 {
-    if (a.cont_count && blockIdx.x == 0 && threadIdx.x < 2) a.cont_count[threadIdx.x] = 0u;
+    if (a.cont_count && blockIdx.x == 0 && threadIdx.x < 2) contCountReset(a.cont_count);
     if (a.cont_bins && blockIdx.x == 0)
         for (int i = threadIdx.x; i < kSortBins; i += 64) a.cont_bins[i] = 0u;
     for (int u = blockIdx.x; u < units; u += gridDim.x) {

@@ -363,6 +363,16 @@ static napi_value QueueStats(napi_env env, napi_callback_info info)
     for (uint32_t i = 0; i < 16; i++) napi_set_element(env, r, i, num(env, q[i]));
     return r;
 }
+/* pt_cont_stats(ctx) -> [records stored for pt_cont, draws that launched it] */
+static napi_value ContStats(napi_env env, napi_callback_info info)
+{
+    napi_value a[MAXARGS], r; if (args(env, info, a, 1) < 0) return NULL;
+    uint64_t s[2] = { 0, 0 };
+    pt_cont_stats((pt_ctx*)handle(env, a[0]), s);
+    CHECK(napi_create_array_with_length(env, 2, &r));
+    for (uint32_t i = 0; i < 2; i++) napi_set_element(env, r, i, num(env, (double)s[i]));
+    return r;
+}
 /* pt_bvh_build(aabbIn: Float32Array (9 per triangle), work: Uint32Array, out: Float32Array) -> node count */
 static napi_value BvhBuild(napi_env env, napi_callback_info info)
 {
@@ -438,7 +448,7 @@ static napi_value Init(napi_env env, napi_value exports)
         { "pt_bvh_layout_used", BvhLayoutUsed }, { "pt_set_stream", SetStream }, { "pt_texture_device_ptr", TexDevicePtr },
         { "pt_last_render_ms", LastRenderMs }, { "pt_timing_begin", TimingBegin }, { "pt_timing_end", TimingEnd },
         { "pt_timing_latency", TimingLatency },
-        { "pt_set_counting", SetCounting }, { "pt_read_counters", ReadCounters }, { "pt_reset_counters", ResetCounters }, { "pt_queue_stats", QueueStats },
+        { "pt_set_counting", SetCounting }, { "pt_read_counters", ReadCounters }, { "pt_reset_counters", ResetCounters }, { "pt_queue_stats", QueueStats }, { "pt_cont_stats", ContStats },
         { "pt_bvh_build", BvhBuild }, { "pt_bvh_build_gpu", BvhBuildGpu },
         { "pt_jpeg_size", JpegSize }, { "pt_jpeg_decode_rgba8", JpegDecode }, { "pt_version", Version },
     };

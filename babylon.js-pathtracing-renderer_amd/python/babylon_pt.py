@@ -40,7 +40,7 @@ SYMBOLS = [
     "pt_render_target_resize", "pt_texture_size", "pt_texture_destroy",
     "pt_render", "pt_read_pixels", "pt_write_pixels",
     "pt_set_row_partition", "pt_set_output_partition", "pt_canvas_wrap", "pt_set_backend", "pt_set_bvh_layout", "pt_bvh_layout_used", "pt_set_stream", "pt_texture_device_ptr", "pt_last_render_ms", "pt_timing_begin", "pt_timing_end", "pt_timing_latency",
-    "pt_set_counting", "pt_read_counters", "pt_reset_counters", "pt_queue_stats", "pt_math_probe", "pt_math_exhaustive", "pt_bvh_build", "pt_bvh_build_gpu", "pt_jpeg_size", "pt_jpeg_decode_rgba8", "pt_version",
+    "pt_set_counting", "pt_read_counters", "pt_reset_counters", "pt_queue_stats", "pt_cont_stats", "pt_math_probe", "pt_math_exhaustive", "pt_bvh_build", "pt_bvh_build_gpu", "pt_jpeg_size", "pt_jpeg_decode_rgba8", "pt_version",
 ]
 
 _lib = None
@@ -89,6 +89,7 @@ def lib():
         "pt_read_counters": ([vp, ctypes.POINTER(ctypes.c_uint64)], i32), "pt_reset_counters": ([vp], i32),
         "pt_math_probe": ([vp, i32, vp, vp, vp, i32], i32),
         "pt_math_exhaustive": ([vp, i32, vp], i32),
+        "pt_cont_stats": ([vp, ctypes.POINTER(ctypes.c_uint64)], i32),
         "pt_queue_stats": ([vp, ctypes.POINTER(ctypes.c_uint32)], i32), "pt_version": ([], ctypes.c_char_p),
     }
     for name, (args, res) in sig.items():
@@ -232,6 +233,13 @@ class Engine:
                 "frames_in_flight": (int(buf[14]) >> 8) & 0xFF,
                 "compacting_draws": int(buf[14]) >> 16,
                 "compaction_trial_ratio": buf[15] / 1000.0 if buf[15] else None}
+
+    def cont_stats(self):
+        """(path records the draws stored for pt_cont, draws that launched pt_cont) since the engine was
+        created, summed over its parts (synchronises)."""
+        buf = (ctypes.c_uint64 * 2)()
+        self.check(lib().pt_cont_stats(self.ctx, buf), "pt_cont_stats")
+        return int(buf[0]), int(buf[1])
 
     def math_probe(self, op, x, y=None):
         x = np.ascontiguousarray(x, dtype=np.float32)

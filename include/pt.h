@@ -232,6 +232,11 @@ int pt_reset_counters(pt_ctx* ctx);
  * out[15] = the auto trial's time with
  * compaction per time without (at the faster depth), x 1000 (0 before the decision). */
 int pt_queue_stats(pt_ctx* ctx, uint32_t out[16]);
+/* Late-bounce compaction totals since the context was created (synchronises): out[0] = the path records
+ * the path-tracing draws stored for the continuation kernel (pt_cont), out[1] = the draws that launched
+ * it (not mod 2^16 as in pt_queue_stats); with several parts, summed over them. Each draw's history
+ * blend adds its record count to the total as it zeroes it, so the path-tracing kernels pay nothing. */
+int pt_cont_stats(pt_ctx* ctx, uint64_t out[2]);
 /* Device self-test of the pinned GLSL built-ins (ops as the oracle's pto_math_probe). */
 int pt_math_probe(pt_ctx* ctx, int op, const float* x, const float* y, float* out, int n);
 /* Exhaustive device self-test of a fast built-in sequence against the IEEE operation it replaces,

@@ -282,6 +282,19 @@ def sky_mesh_stream(material=3, model_inv=None):
     return meta
 
 
+def _with_material(meta, material):
+    """A recorded glTF stream with the model's material switched (uModelMaterialType)."""
+    frames = []
+    for f in meta["frames"]:
+        fr = []
+        for c in f:
+            if c["shader"] == "pathTracingFragmentShader":
+                c = dict(c, uniforms=dict(c["uniforms"], uModelMaterialType=["i", [material]]))
+            fr.append(c)
+        frames.append(fr)
+    return dict(meta, frames=frames)
+
+
 def po_screen_output(acc, one_over_n, exposure=1.0):
     """The oracle's screenOutput (js/PathTracingCommon.js:19-309) of an RGBA32F frame -> RGBA8."""
     import ptoracle as po

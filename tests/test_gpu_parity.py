@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import helpers as H
+from helpers import _with_material
 
 pytestmark = pytest.mark.gpu
 
@@ -902,19 +903,6 @@ def test_sky_mesh_bitexact_and_counters(engine, backend, material):
         assert _bits_equal(rc, gc), "frame %d canvas: %s" % (i, _diff_report(rc, gc))
     assert cnt == {k: sum(c[k] for c in ref_cnt) for k in ref_cnt[0]}
     assert sum(c["hit_lookups"] for c in ref_cnt) > 0
-
-
-def _with_material(meta, material):
-    """A recorded glTF stream with the model's material switched (uModelMaterialType)."""
-    frames = []
-    for f in meta["frames"]:
-        fr = []
-        for c in f:
-            if c["shader"] == "pathTracingFragmentShader":
-                c = dict(c, uniforms=dict(c["uniforms"], uModelMaterialType=["i", [material]]))
-            fr.append(c)
-        frames.append(fr)
-    return dict(meta, frames=frames)
 
 
 @pytest.mark.parametrize("scene", ["gltf_teapot", "sky_dragon"])
