@@ -10,9 +10,13 @@ same previousBuffer, and writes
                                              oracle to, on hosts without /root/reference)
   tests/golden/xcheck/report.json            per stream: pixels compared, pixels whose RGBA32F
                                              bits differ, max |difference|, RMSE
+  tests/golden/xcheck/variants_<scene>.npz   (--variants) the same for the settings the pages' GUIs
+                                             reach (tests/settings_variants.py): "<variant>/acc<k>";
+                                             their comparisons go under report.json's "_variants"
 
 usage: run_xcheck.py [stream ...]   (default: every recorded stream of a reference shader)
        run_xcheck.py --build          (only transcribe and compile every scene into oracle/_ref/)
+       run_xcheck.py --variants       (only the setting variants; the other fixtures stay as they are)
 """
 import ctypes
 import json
@@ -157,6 +161,38 @@ def run_output():
         json.dump(report, f, indent=1, sort_keys=True)
 
 
+def run_variants():
+    """Every setting variant whose page has a reference shader, through the transcription: the
+    protocol of run() (each frame alone, on the oracle's history), one npz per scene."""
+    import settings_variants as S
+    rpath = os.path.join(GOLD, "report.json")
+    report = json.load(open(rpath))
+    report["_variants"] = {}
+    for base in S.XCHECK_BASES:
+        meta = S.base_meta(base)
+        scene = meta["scene"]
+        lib, _ = build(scene)
+        outs = {}
+        for name in S.variants_of(base):
+            _, _, w, h, frames = S.VARIANTS[name]
+            ref_accs = S.oracle(name)["acc"]
+            xs = XScene(lib, meta, w, h, None)
+            prev = np.zeros((h, w, 4), np.float32)
+            per_frame = []
+            for k in range(frames):
+                got = xs.frame(S.uniforms(name, k), prev)
+                outs["%s/acc%d" % (name, k)] = got
+                c = compare(ref_accs[k], got)
+                per_frame.append({"pixels_differing": c["pixels_differing"], "max_abs": c["max_abs"]})
+                prev = ref_accs[k]
+            report["_variants"][name] = {"base": base, "scene": scene, "width": w, "height": h, "frames": frames,
+                                         "per_frame": per_frame}
+            print(name, json.dumps(per_frame), flush=True)
+        np.savez_compressed(os.path.join(GOLD, "variants_%s.npz" % scene), **outs)
+    with open(rpath, "w") as f:
+        json.dump(report, f, indent=1, sort_keys=True)
+
+
 def run(names):
     os.makedirs(GOLD, exist_ok=True)
     rpath = os.path.join(GOLD, "report.json")
@@ -195,6 +231,8 @@ if __name__ == "__main__":
             print("built oracle/_ref/libxcheck_%s.so" % sc)
     elif sys.argv[1:] == ["--output"]:
         run_output()
+    elif sys.argv[1:] == ["--variants"]:
+        run_variants()
     else:
         run(sys.argv[1:] or list(STREAMS))
         if not sys.argv[1:]:
