@@ -5,16 +5,11 @@
 #include <stdint.h>
 
 #include "pt_glsl.h"
+#include "pt_plan.h"   // kBlock, kTile, kSplitParts, kOrderHeld, kSortBins: the constants the host's schedule shares
 
 namespace pt {
 
-constexpr int kBlock = 256;          // 4 waves; a block shades a 16x16 pixel tile
-constexpr int kTile = 16;            // tile edge == row-band height used for sharding
 constexpr int kWaveLogSlots = 13;   // experiment builds (PT_SECPROF): u64 per workgroup in TraceArgs::wave_log
-// split tiles (pt_trace, longest-first): each 8x8 quadrant of a split 16x16 tile is shaded by this
-// many waves of 64 / kSplitParts lanes (4x4-pixel waves of 16 lanes; one 2x2 quad per wave measured
-// slower)
-constexpr unsigned kSplitParts = 4;
 constexpr int kStackLevels = 28;     // stackLevels[28], js/GLTFModelPathTracing_FragmentShader.js:95
 // BVH stack levels kept in LDS per lane (deeper levels go to a global slab): 7 for the 4-wave variants;
 // the child-pair walk of the texture-free mesh programs runs at 8 waves/SIMD (pt_device.h kMinWaves),
@@ -211,7 +206,6 @@ struct WfBufs {
     int wq, hq;             // quad-rounded frame size
 };
 
-constexpr unsigned kOrderHeld = 128;   // pt_order_build: tiles per thread kept in registers (a byte each)
 // the longest-first order build of a megakernel draw (pt_kernels.hip orderBuild): as its own kernel
 // (pt_order_build) or as the extra block of the next screenOutput pass (OutputArgs::ob)
 struct OrderArgs {
@@ -257,7 +251,6 @@ struct BlendArgs {
 };
 
 // (PT_CONT_SORT) pt_cont's records ordered by a ray key (pt_kernels.hip pt_cont_hist / pt_cont_scatter)
-constexpr int kSortBins = 8192;   // at most: light flag x 8 octants x 8^3 cells
 constexpr unsigned kSortChunk = 512;   // records per pt_cont_scatter workgroup (2048: ±0, 8192: -1 to -5 %)
 struct SortArgs {
     const unsigned* count;        // [0] records stored by the draw

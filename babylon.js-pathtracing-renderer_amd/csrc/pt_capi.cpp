@@ -1,15 +1,25 @@
 // pt_capi.cpp — one device's part of a libpt context (pt_dev.h): contexts, effects, textures,
-// render targets and draws on one HIP stream of one gfx950 device, mirroring the Babylon effect API
-// the reference's setup scripts call. The exported C ABI (include/pt.h, pt_group.cpp) drives one
-// such part per device of a context and fans every call out over them.
+// render targets and draws on one gfx950 device, mirroring the Babylon effect API the reference's
+// setup scripts call. The exported C ABI (include/pt.h, pt_group.cpp) drives one such part per device
+// of a context and fans every call out over them.
 //
 // What happens on dev_render(effect, target), per recognised program:
-//   CORNELL / GLTF  -> uniforms resolved by name, SetupScene() evaluated once on the host with the
-//                      same IEEE ops as the GLSL, one pt_trace launch over the 16-row bands this
-//                      context owns (dev_set_row_partition);
-//   SCREEN_COPY     -> pt_copy over the owned bands;
-//   SCREEN_OUTPUT   -> pt_output into the canvas (RGBA8) or an RGBA32F target.
-// Everything is enqueued on the context's stream; HIP events bracket every draw for timing.
+//   path tracing    -> (Cornell, quadrics, sky, sky + mesh, HDRI, glTF) uniforms resolved by name and
+//                      SetupScene() evaluated once on the host with the same IEEE ops as the GLSL
+//                      (trace_args), then the context's schedule over the 16-row bands it owns
+//                      (dev_set_row_partition). The megakernel, the default (draw_mega): pt_trace, with
+//                      late-bounce compaction the record sort and pt_cont, on one of the side streams,
+//                      up to `depth` frames in flight, each gated by a mark on the main stream; then
+//                      pt_blend on the main stream, and the longest-first order build deferred into the
+//                      next screenOutput. Which buffer set, stream and mark, the grid and whether the
+//                      draw compacts is pt_plan.h's arithmetic; this file reserves memory and issues
+//                      the HIP calls. The wavefront and persistent schedules (draw_queued) run on the
+//                      main stream alone;
+//   SCREEN_COPY     -> pt_copy over the owned bands, deferred to fuse with the next screenOutput;
+//   SCREEN_OUTPUT   -> pt_output into the canvas (RGBA8) or an RGBA32F target, with a deferred copy
+//                      and order build riding along.
+// The main stream is the context's own or the caller's (dev_set_stream); per-draw timing events are off
+// until asked for (pt_last_render_ms, the timing window).
 #include "../../include/pt.h"
 
 #include <hip/hip_runtime.h>
@@ -26,6 +36,7 @@
 
 #include "pt_args.h"
 #include "pt_knobs.h"
+#include "pt_plan.h"
 #include "pt_dev.h"
 
 extern "C" {
@@ -142,7 +153,6 @@ struct Dev {
     // Depth (k.depth, 2-6): side streams; draw k waits for the mark draw k - depth - lag + 1
     // recorded (depth 2, lag 0: the previous draw's), so up to `depth` frames' path tracing are in flight.
     static constexpr int kDepthMax = pt::kDepthMax;
-    int depth_run = 3;            // the last megakernel draw's depth (<= k.depth: the auto trial may pick 2)
     // Lag (k.lag): buffer sets beyond the streams. Draw k's buffer set is k % (depth + lag)
     // (radiance, compaction records, longest-first cost / order: what the main stream's blend, output
     // and order build read) and its stream / spill slab k % depth (what only its own stream touches),
@@ -150,13 +160,10 @@ struct Dev {
     // draw as soon as its previous one ends, not after that draw's blend and output on the main stream.
     // By default (lag -1) the lag is kLagSmall for draws that trace fewer than k.lag_pixels pixels and
     // 0 above.
-    static constexpr int kLagMax = pt::kLagMax, kSetsMax = kDepthMax + kLagMax, kLagSmall = 2;
-    int lag_run = 0;              // the last megakernel draw's lag
+    static constexpr int kLagMax = pt::kLagMax, kSetsMax = kDepthMax + kLagMax;
     hipStream_t ts[kDepthMax] = {};
     hipEvent_t ev_mark[kSetsMax] = {}, ev_traced[kDepthMax] = {};
-    unsigned mk_seq = 0;          // megakernel draws so far (buffer set mk_seq % (depth + lag), stream mk_seq % depth)
-    bool need_fresh = true;       // the next megakernel draw must wait for everything before it (a fresh mark)
-    unsigned mark_floor = 0;      // no draw waits for a mark older than draw mark_floor's
+    pt::Overlap ov;               // which draw this is, its buffer set, stream and mark (pt_plan.h)
     float4* rad_mem = nullptr;    // rad[sets()]: radiance + flag per pixel
     size_t rad_pixels = 0;
     // late-bounce compaction of the megakernel's mesh draws (pt_trace<P,false,true> -> pt_cont; k.cont_mode):
@@ -165,28 +172,9 @@ struct Dev {
     size_t cont_cap = 0;          // records per buffer set ...
     int cont_sets = 0;            // ... and buffer sets allocated
     uint64_t cont_stored = 0;     // records stored by draws of earlier allocations (pt_cont_stats; cont_reserve)
-    // auto mode: compaction pays on the heavy 4K frames (sky + dragon +19 %, dragon stand-in +10 %) and
-    // costs elsewhere (bunny 4K -22 %, helmet -9 %, rank-sized frames -29 %: profiles/r05i_*), which
-    // the draw's arguments do not tell apart. So the draws of one target / program / partition time it:
-    // after kContSkip draws (the last two compacting, to warm it up on the side streams), blocks of
-    // kContBlock draws with it on and off, kContMeasured draws inside each timed by events on the main
-    // stream; at the trial's end the host waits for it once, and compaction stays on only if its faster
-    // block took 2 % less time than the faster block without. Same bits either way.
-    // The blocks without compaction also try two frames in flight instead of three (on, off, off at
-    // depth 2 twice, off, on): the light frames that do not compact lost 2-5 % to the third frame
-    // (r05q: bunny 5365 vs 5228 Mpaths/s, bunny16 -4.5 %), so the faster depth stays with "off".
-    struct ContTune {
-        const void* target; int prog, part, parts, w, h;
-        int seen;                 // megakernel draws of this key so far
-        bool decided, choice;
-        int depth;                // the frames in flight the decision keeps
-        float ms_on, ms_off, ms_off2;
-    } tune = {};
-    // the trial starts at the 33rd draw of a target: short runs (the driver's 5 + 20 frames) stay in the
-    // default, longer ones settle on the measured best
-    static constexpr int kContSkip = 32, kContBlock = 10, kContSettle = 3, kContMeasured = 5, kContBlocks = 6;
-    hipEvent_t tune_ev[2 * kContBlocks] = {};
-    int cont_last = 0;   // what the last megakernel draw did (cont_decide)
+    pt::ContTrial trial;          // auto mode: the draws of one target time it on and off (pt_plan.h)
+    hipEvent_t tune_ev[2 * pt::kContBlocks] = {};   // ... by these events on the main stream
+    int cont_last = 0;   // what the last megakernel draw did (pt::ContTrial::Draw::code)
     unsigned cont_draws = 0;   // megakernel draws that launched pt_cont, since the context was created
     pt::WfBufs gb = {};           // persistent backend: per-pixel G-buffer + radiance
     void* gb_mem = nullptr;
@@ -204,7 +192,7 @@ struct Dev {
     unsigned* lpt_cost(int p) const { return lpt_mem + 4 * lpt_cap * p; }
     unsigned* lpt_order(int p) const { return lpt_mem + 4 * lpt_cap * kSetsMax + lpt_cap * p; }
     unsigned* lpt_split(int p) const { return lpt_mem + 5 * lpt_cap * kSetsMax + p; }
-    int sets() const { return k.depth + (k.lag >= 0 ? k.lag : kLagSmall); }   // buffer sets allocated (rad, compaction records)
+    int sets() const { return k.depth + (k.lag >= 0 ? k.lag : pt::kLagSmall); }   // buffer sets allocated (rad, compaction records)
     // per-draw events for pt_last_render_ms: off until its first call (or k.draw_events)
     bool draw_events = false;
     hipEvent_t ev0[kProgSlots] = {}, ev1[kProgSlots] = {};
@@ -395,12 +383,7 @@ void setup_scene(const DevFx* fx, pt::TraceArgs& a)
     }
 }
 
-int bands_owned(const Dev* c, int height)
-{
-    int nb = (height + pt::kTile - 1) / pt::kTile;
-    if (c->part >= nb) return 0;
-    return (nb - c->part + c->num_parts - 1) / c->num_parts;
-}
+int bands_owned(const Dev* c, int height) { return pt::bands_owned(height, c->num_parts, c->part); }
 
 int begin_draw(Dev* c, int prog, hipStream_t s = nullptr)
 {
@@ -438,6 +421,27 @@ int end_draw(Dev* c, int prog, hipStream_t s = nullptr)
     return PT_OK;
 }
 
+// Grow a device allocation: wait for the streams whose work may still use the old one, free it, allocate
+// `bytes` and record its new size (0 while there is none). WAIT_ALL: the side streams' path tracing uses it too.
+// `fresh`: the megakernel's draws use it, so the next one waits for everything before it (new memory).
+enum SlabWait { WAIT_MAIN, WAIT_ALL };
+template <class T>
+int slab_grow(Dev* c, T*& mem, size_t& size, size_t new_size, size_t bytes, SlabWait wait, bool fresh)
+{
+    if (mem) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (int p = 0; wait == WAIT_ALL && p < Dev::kDepthMax; p++)
+            if (c->ts[p]) HIPCHK(c, hipStreamSynchronize(c->ts[p]));
+        HIPCHK(c, hipFree(mem));
+        mem = nullptr;
+    }
+    size = 0;
+    HIPCHK(c, hipMalloc(&mem, bytes));
+    size = new_size;
+    if (fresh) c->ov.need_fresh = true;
+    return PT_OK;
+}
+
 // (re)allocate the wavefront buffers for `tiles` 16x16 tiles of a wq x hq quad-rounded frame and
 // a persistent grid of `blocks` blocks: one slab, carved into the WfBufs arrays
 int wf_reserve(Dev* c, int wq, int hq, int tiles, int blocks)
@@ -450,12 +454,11 @@ int wf_reserve(Dev* c, int wq, int hq, int tiles, int blocks)
         c->wf.shard_cap = cap; c->wf.wq = wq; c->wf.hq = hq;
         return PT_OK;
     }
-    if (c->wf_mem) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(c->wf_mem)); c->wf_mem = nullptr; }
     const size_t f4s = slots * sizeof(float4), f4p = pixels * sizeof(float4);
     const size_t bytes = 4096 + 10 * f4s + 3 * f4p + slots * sizeof(unsigned) + spill * sizeof(float2) + 16 * 256;
-    HIPCHK(c, hipMalloc(&c->wf_mem, bytes));
+    if (int rc = slab_grow(c, c->wf_mem, c->wf_slots, slots, bytes, WAIT_MAIN, false)) return rc;
     char* m = (char*)c->wf_mem;
-    auto take = [&](size_t n) { char* r = m; m += (n + 255) & ~(size_t)255; return r; };
+    auto take = [&](size_t n) { char* r = m; m += pt::align256(n); return r; };
     c->wf.cnt = (unsigned*)take(4096);
     c->wf.bcnt = c->wf.cnt + 8 * pt::kShards;
     for (int k = 0; k < 2; k++) {
@@ -466,7 +469,7 @@ int wf_reserve(Dev* c, int wq, int hq, int tiles, int blocks)
     c->wf.gb0 = (float4*)take(f4p); c->wf.gb1 = (float4*)take(f4p); c->wf.rad = (float4*)take(f4p);
     c->wf.bvhq = (unsigned*)take(slots * sizeof(unsigned));
     c->wf.spill = (float2*)take(spill * sizeof(float2));
-    c->wf_slots = slots; c->wf_pixels = pixels; c->wf_spill = spill;
+    c->wf_pixels = pixels; c->wf_spill = spill;
     c->wf.shard_cap = cap; c->wf.wq = wq; c->wf.hq = hq;
     return PT_OK;
 }
@@ -479,12 +482,8 @@ constexpr size_t kSpillPerLane = pt::kStackLevels - pt::kStackLdsMin + 4;   // f
 int spill_reserve(Dev* c, size_t lanes)
 {
     if (lanes <= c->mk_spill_lanes) return PT_OK;
-    if (c->mk_spill) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(c->mk_spill)); c->mk_spill = nullptr; }
-    c->mk_spill_lanes = 0;
-    HIPCHK(c, hipMalloc(&c->mk_spill, (size_t)c->k.depth * lanes * kSpillPerLane * sizeof(float2)));
-    c->mk_spill_lanes = lanes;
-    c->need_fresh = true;   // new memory: the next draw waits for everything before it
-    return PT_OK;
+    return slab_grow(c, c->mk_spill, c->mk_spill_lanes, lanes, (size_t)c->k.depth * lanes * kSpillPerLane * sizeof(float2),
+                     WAIT_MAIN, true);
 }
 float2* spill_slab(Dev* c, int p) { return c->mk_spill + (size_t)p * c->mk_spill_lanes * kSpillPerLane; }
 
@@ -492,48 +491,28 @@ float2* spill_slab(Dev* c, int p) { return c->mk_spill + (size_t)p * c->mk_spill
 int rad_reserve(Dev* c, size_t pixels)
 {
     if (pixels <= c->rad_pixels) return PT_OK;
-    if (c->rad_mem) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(c->rad_mem)); c->rad_mem = nullptr; }
-    c->rad_pixels = 0;
-    HIPCHK(c, hipMalloc(&c->rad_mem, (size_t)c->sets() * pixels * sizeof(float4)));
-    c->rad_pixels = pixels;
-    c->need_fresh = true;
-    return PT_OK;
+    return slab_grow(c, c->rad_mem, c->rad_pixels, pixels, (size_t)c->sets() * pixels * sizeof(float4), WAIT_MAIN, true);
 }
 
-// the overlap lag of a draw that traces `traced` pixels (Knobs::lag)
-int draw_lag(const Dev* c, size_t traced) { return c->k.lag >= 0 ? c->k.lag : traced < (size_t)c->k.lag_pixels ? Dev::kLagSmall : 0; }
-
-// the pixels a draw of `target` traces: the owned 16-row bands of the partition (a bound on its records)
-size_t traced_pixels(const Dev* c, const DevTex* target)
-{
-    const int nb = (target->h + pt::kTile - 1) / pt::kTile;
-    const int own = c->part < nb ? (nb - c->part + c->num_parts - 1) / c->num_parts : 0;
-    return std::min((size_t)target->w * target->h, (size_t)own * pt::kTile * target->w);
-}
+// the pixels a draw of `target` traces: the owned bands, a bound on its records, and about, for the measured
+// thresholds (pt_plan.h: the two are not interchangeable)
+size_t owned_pixels(const Dev* c, const DevTex* target) { return pt::owned_pixels(target->w, target->h, c->num_parts, c->part); }
+size_t share_pixels(const Dev* c, const DevTex* target) { return pt::share_pixels(target->w, target->h, c->num_parts); }
 
 // pt_cont's records for draws that trace up to `paths` pixels (a record per traced pixel at most), in `sets`
-// buffer sets: per set records [cap x 64 B] | pixels [cap x 4 B] | counter; the counters start at zero here,
-// afterwards each draw's pt_blend zeroes its own. (Sized by the partition's pixels and the sets its draws
-// cycle through, not the whole target times every set: a 4K frame's records are 0.53 GB per set.)
-// bytes of one buffer set for `paths` records: records [paths x 64 B] | pixels [x 4 B] | (PT_CONT_SORT: order
-// [x 4 B] | ranks [x 4 B] | keys [x 2 B] | the keys' totals) | counter
-size_t cont_bytes(const Dev* c, size_t paths)
-{
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    size_t per = paths * 64 + al(paths * 4) + 256;
-    if (c->k.cont_sort) per += 2 * al(paths * 4) + al(paths * 2) + pt::kSortBins * 4;
-    return per;
-}
+// buffer sets, each laid out by pt::ContLayout; the counters start at zero here, afterwards each draw's pt_blend
+// zeroes its own. (Sized by the partition's pixels and the sets its draws cycle through, not the whole target
+// times every set: a 4K frame's records are 0.53 GB per set.)
+pt::ContLayout cont_layout(const Dev* c) { return pt::ContLayout(c->cont_cap, c->k.cont_sort != 0); }
 // the records the draws of the current allocation stored: the buffer sets' running totals, which each draw's
 // pt_blend keeps in its counter block (the main stream must be idle)
 int cont_totals(Dev* c, uint64_t* sum)
 {
     *sum = 0;
-    const size_t per = cont_bytes(c, c->cont_cap);
+    const pt::ContLayout L = cont_layout(c);
     for (int p = 0; c->cont_mem && p < c->cont_sets; p++) {
         uint64_t v = 0;
-        HIPCHK(c, hipMemcpy(&v, (char*)c->cont_mem + (size_t)(p + 1) * per - 256 + 2 * sizeof(unsigned), sizeof(v),
-                            hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(&v, (char*)c->cont_mem + (size_t)p * L.bytes + L.total(), sizeof(v), hipMemcpyDeviceToHost));
         *sum += v;
     }
     return PT_OK;
@@ -548,126 +527,59 @@ int cont_reserve(Dev* c, size_t paths, int sets)
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (int rc = cont_totals(c, &stored)) return rc;
         c->cont_stored += stored;
-        HIPCHK(c, hipFree(c->cont_mem));
-        c->cont_mem = nullptr;
     }
-    c->cont_cap = 0;
     c->cont_sets = 0;
-    const size_t per = cont_bytes(c, paths);
-    HIPCHK(c, hipMalloc(&c->cont_mem, (size_t)sets * per));
+    const size_t bytes = (size_t)sets * pt::ContLayout(paths, c->k.cont_sort != 0).bytes;
+    if (int rc = slab_grow(c, c->cont_mem, c->cont_cap, paths, bytes, WAIT_MAIN, true)) return rc;
+    c->cont_sets = sets;
     // on the main stream (hipMemset would go to the null stream, which the non-blocking side streams do
     // not wait for: the next draw's atomics raced with it); the next draw's path tracing waits for a mark
     // recorded after it
-    HIPCHK(c, hipMemsetAsync(c->cont_mem, 0, (size_t)sets * per, c->stream));
-    c->cont_cap = paths;
-    c->cont_sets = sets;
-    c->need_fresh = true;
+    HIPCHK(c, hipMemsetAsync(c->cont_mem, 0, bytes, c->stream));
     return PT_OK;
 }
-void cont_args(Dev* c, int p, pt::TraceArgs& a)
+// buffer set p's records as the draw's arguments; `sort`: with the arrays of the record sort (else NULL)
+void cont_args(Dev* c, int p, bool sort, pt::TraceArgs& a)
 {
-    const size_t per = cont_bytes(c, c->cont_cap);
-    char* m = (char*)c->cont_mem + (size_t)p * per;
-    a.cont_rec = (float4*)m;
-    a.cont_aux = (unsigned*)(m + c->cont_cap * 64);
-    a.cont_count = (unsigned*)(m + per - 256);
-    a.cont_perm = nullptr;
-    a.cont_rank = nullptr;
-    a.cont_key = nullptr;
-    a.cont_bins = nullptr;
+    const pt::ContLayout L = cont_layout(c);
+    char* m = (char*)c->cont_mem + (size_t)p * L.bytes;
+    a.cont_rec = (float4*)(m + L.rec);
+    a.cont_aux = (unsigned*)(m + L.aux);
+    a.cont_count = (unsigned*)(m + L.count);
+    a.cont_perm = sort ? (unsigned*)(m + L.perm) : nullptr;
+    a.cont_rank = sort ? (unsigned*)(m + L.rank) : nullptr;
+    a.cont_key = sort ? (unsigned short*)(m + L.key) : nullptr;
+    a.cont_bins = sort ? (unsigned*)(m + L.bins) : nullptr;
     a.cont_bounce = (unsigned)c->k.cont_bounce;   // (>= 2: the G-buffer's normal / colour / id are final from bounce 2)
     a.cont_lanes = (unsigned)c->k.cont_lanes;
     a.cont_refill = (unsigned)c->k.cont_refill;
 }
 
-// auto mode of late-bounce compaction (Dev::ContTune): whether this draw compacts. `alone`: a moving-camera
-// draw that runs alone and never compacts (render_trace) is no draw of the trial - it leaves the tune as it
-// is (not counted, no event) and only takes the frames in flight a still draw in its place would
-int cont_decide_(Dev* c, const DevTex* target, int prog, bool eligible, bool alone, bool* on, int* depth)
+// Whether this draw compacts, and its frames in flight: pt::ContTrial decides; here the records, the auto trial's
+// events on the main stream and the one wait at its end. `alone`: a moving-camera draw that runs alone (draw_mega).
+int cont_decide(Dev* c, const DevTex* target, int prog, bool eligible, bool alone, pt::ContTrial::Draw* d)
 {
-    *on = false;
-    *depth = c->k.depth;
-    if (!eligible || c->k.cont_mode == 0) return PT_OK;
+    const size_t share = share_pixels(c, target);
     // the records first, so that no trial block pays for their allocation (for every set the draws of this
     // target cycle through: the depth, at most k.depth, plus the lag)
-    const size_t traced_approx = (size_t)target->w * target->h / (size_t)std::max(1, c->num_parts);   // (as render_trace's)
-    if (int rc = cont_reserve(c, traced_pixels(c, target), c->k.depth + draw_lag(c, traced_approx))) return rc;
-    if (c->k.cont_mode == 1) { *on = true; return PT_OK; }
-    auto& t = c->tune;
-    bool same = t.target == target && t.prog == prog && t.part == c->part && t.parts == c->num_parts && t.w == target->w &&
-                t.h == target->h;
-    if (!same && !alone) {
-        t = Dev::ContTune{ target, prog, c->part, c->num_parts, target->w, target->h, 0, false, false, c->k.depth,
-                           0.0f, 0.0f, 0.0f };
-        same = true;
-    }
-    const int i = (alone ? (same ? t.seen : 0) : t.seen++) - Dev::kContSkip;
-    if (same && t.decided) { *on = t.choice; *depth = t.depth; return PT_OK; }
-    // before the trial, the default: on for frames of at least cont_auto_pixels (with three frames in
-    // flight it won on every frame of 2 MP and more but the light bunny, and lost on the rank-sized one,
-    // profiles/r05q_frames_depth_x_compaction.txt); the two draws before the trial compact, one per side
-    // stream of the last two buffer sets, whatever the default: the first launch of a variant that needs
-    // more scratch than any before it waits for the device to drain while the runtime grows its scratch
-    // (r05k: the first trial block then took 2-8x the others)
-    if (i < 0) {
-        // (the pixels this partition traces: a rank's bands of an N-GPU frame are a small frame -
-        // r05ao: 0.5-1 Mpx frames lost 33-41 % to compaction)
-        const size_t traced = (size_t)target->w * target->h / (size_t)std::max(1, c->num_parts);
-        *on = traced >= (size_t)c->k.cont_auto_pixels || i >= -2;
-        // without compaction, frames of lag_pixels and more keep two frames in flight (r05aw: the
-        // 4K frame's eighth at N = 8 +5.6 %; r05y: StanfordBunny 1080p +3.5 %), smaller ones three
-        // and the lag (a 1920x136 frame: two lost a third, r05aa)
-        if (!*on && !c->k.depth_env && traced >= (size_t)c->k.lag_pixels) *depth = std::min(2, c->k.depth);
-        return PT_OK;
-    }
-    constexpr int B = Dev::kContBlock, S = Dev::kContSettle, M = Dev::kContMeasured, trial = Dev::kContBlocks * B;
-    // each block times draws S .. S + M - 1 of its own: an event on the main stream (the work before the
-    // draw: the previous draw's blend, which waited for its path tracing) at the block's offsets S and
-    // S + M. With up to `depth` frames in flight, S draws settle the switch (buffer sets whose
-    // longest-first order came from the other mode's costs) and the block's last B - S - M draws keep the
-    // next block's frames out of the timed ones.
-    const int b = i / B, o = i % B;
-    if (i < trial && (o == S || o == S + M) && !alone) {
-        hipEvent_t& e = c->tune_ev[2 * b + (o == S ? 0 : 1)];
+    if (eligible && c->k.cont_mode != 0)
+        if (int rc = cont_reserve(c, owned_pixels(c, target), c->k.depth + pt::draw_lag(c->k, share))) return rc;
+    *d = c->trial.draw({ target, prog, c->part, c->num_parts, target->w, target->h }, eligible, alone, share, c->k);
+    if (d->event >= 0) {
+        hipEvent_t& e = c->tune_ev[d->event];
         if (!e) HIPCHK(c, hipEventCreate(&e));
         HIPCHK(c, hipEventRecord(e, c->stream));
     }
-    if (i < trial) {
-        *on = b == 0 || b == Dev::kContBlocks - 1;   // on, off, off at depth 2 (twice), off, on
-        if (b == 2 || b == 3) *depth = std::min(2, c->k.depth);
-        return PT_OK;
+    if (d->ends) {
+        // the host waits for the trial once (the draws it has already queued ran without), so that every later
+        // draw of this target takes the decision
+        HIPCHK(c, hipEventSynchronize(c->tune_ev[2 * pt::kContBlocks - 1]));
+        float ms[pt::kContBlocks] = {};
+        for (int b = 0; b < pt::kContBlocks; b++) HIPCHK(c, hipEventElapsedTime(&ms[b], c->tune_ev[2 * b], c->tune_ev[2 * b + 1]));
+        *d = c->trial.conclude(ms);
     }
-    if (alone) return PT_OK;   // (the next still draw ends the trial)
-    // the trial's end: the host waits for it once (the draws it has already queued ran without), so that
-    // every later draw of this target takes the decision; the faster block of each mode decides (one
-    // stray block cannot)
-    HIPCHK(c, hipEventSynchronize(c->tune_ev[2 * Dev::kContBlocks - 1]));
-    t.ms_on = t.ms_off = t.ms_off2 = 1e30f;
-    for (int k = 0; k < Dev::kContBlocks; k++) {
-        float ms = 0.0f;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->tune_ev[2 * k], c->tune_ev[2 * k + 1]));
-        float& m = k == 0 || k == Dev::kContBlocks - 1 ? t.ms_on : k == 2 || k == 3 ? t.ms_off2 : t.ms_off;
-        m = std::min(m, ms);
-    }
-    t.decided = true;
-    const bool two = t.ms_off2 < t.ms_off;
-    t.choice = t.ms_on < 0.98f * std::min(t.ms_off, t.ms_off2);
-    t.depth = t.choice || !two ? c->k.depth : std::min(2, c->k.depth);
-    *on = t.choice;
-    *depth = t.depth;
+    c->cont_last = d->code;
     return PT_OK;
-}
-
-int cont_decide(Dev* c, const DevTex* target, int prog, bool eligible, bool alone, bool* on, int* depth)
-{
-    int rc = cont_decide_(c, target, prog, eligible, alone, on, depth);
-    if (alone) *on = false;
-    // what the draw did, for pt_queue_stats: 0 off, 1 auto decided off, 2 auto decided on, 3 forced on,
-    // 4 auto trial
-    const bool tried = c->k.cont_mode == 2 && eligible && !alone;
-    c->cont_last = c->k.cont_mode == 1 && *on ? 3 : !tried ? 0 : c->tune.decided ? (c->tune.choice ? 2 : 1)
-                 : c->tune.seen > Dev::kContSkip ? 4 : (*on ? 5 : 6);
-    return rc;
 }
 
 // the side streams and events of frame overlap (created at the first overlapped draw)
@@ -686,14 +598,11 @@ int gb_reserve(Dev* c, int wq, int hq)
 {
     const size_t pixels = (size_t)wq * hq;
     if (pixels > c->gb_pixels) {
-        if (c->gb_mem) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(c->gb_mem)); c->gb_mem = nullptr; }
-        c->gb_pixels = 0;
-        const size_t f4p = ((pixels * sizeof(float4)) + 255) & ~(size_t)255;
-        HIPCHK(c, hipMalloc(&c->gb_mem, 3 * f4p));
+        const size_t f4p = pt::align256(pixels * sizeof(float4));
+        if (int rc = slab_grow(c, c->gb_mem, c->gb_pixels, pixels, 3 * f4p, WAIT_MAIN, false)) return rc;
         c->gb.gb0 = (float4*)c->gb_mem;
         c->gb.gb1 = (float4*)((char*)c->gb_mem + f4p);
         c->gb.rad = (float4*)((char*)c->gb_mem + 2 * f4p);
-        c->gb_pixels = pixels;
     }
     c->gb.wq = wq; c->gb.hq = hq;
     return PT_OK;
@@ -737,7 +646,7 @@ bool ensure_pairs(Dev* c, DevTex* t, const DevTex* tri, int* rc)
     t->pairs_gen = t->gen; t->pairs_tri = tri; t->pairs_tri_gen = tri->gen;
     const unsigned nrec = (unsigned)((texels + 1) / 2);
     const unsigned nblk = (nrec + 1023) / 1024;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    constexpr auto al = pt::align256;
     unsigned char *inner = nullptr, *leafref = nullptr, *scratch = nullptr;
     unsigned* counts = nullptr;
     float* code = nullptr;
@@ -823,17 +732,17 @@ int flush_order(Dev* c)
     return PT_OK;
 }
 
-int render_trace(DevFx* fx, DevTex* target)
+// A path-tracing draw's arguments from the effect's uniforms and samplers, checked; `mesh`: the program walks a BVH
+// (whose child-pair records are built here when its textures changed)
+int trace_args(DevFx* fx, DevTex* target, pt::TraceArgs& a, bool& mesh)
 {
     Dev* c = fx->ctx;
-    if (int rc = flush_order(c)) return rc;   // this draw's order (before lpt_mem could be reallocated)
     if (!target || target->kind != TEX_RT) return fail(c, PT_ERR_ARG, "path tracing draws need a render target");
     DevTex* prev = sampler(fx, "previousBuffer");
     DevTex* bn = sampler(fx, "blueNoiseTexture");
     if (!prev || prev->kind == TEX_U8 || prev->w != target->w || prev->h != target->h)
         return fail(c, PT_ERR_STATE, "previousBuffer must be an RGBA32F texture of the target's size");
     if (!bn || bn->kind != TEX_U8) return fail(c, PT_ERR_STATE, "blueNoiseTexture must be bound (RGBA8)");
-    pt::TraceArgs a;
     std::memset(&a, 0, sizeof(a));
     a.width = target->w;
     a.height = target->h;
@@ -852,7 +761,7 @@ int render_trace(DevFx* fx, DevTex* target)
     a.prev = (const float4*)prev->d;
     a.out = (float4*)target->d;
     a.bluenoise = tex8(bn);
-    const bool mesh = fx->prog == PT_PROG_GLTF || fx->prog == PT_PROG_HDRI || fx->prog == PT_PROG_SKY_MESH;
+    mesh = fx->prog == PT_PROG_GLTF || fx->prog == PT_PROG_HDRI || fx->prog == PT_PROG_SKY_MESH;
     if (mesh) {
         DevTex* bvh = sampler(fx, "tAABBTexture");
         DevTex* tri = sampler(fx, "tTriangleTexture");
@@ -902,8 +811,14 @@ int render_trace(DevFx* fx, DevTex* target)
         a.walk_stat = walkstat ? g_walk_stat : nullptr;
     }
 #endif
-    int gx = (target->w + pt::kTile - 1) / pt::kTile;
-    int gy = bands_owned(c, target->h);
+    return PT_OK;
+}
+
+// The wavefront / persistent schedules (and a draw that owns no band) over gx x gy tiles: on the main stream,
+// their finish pass accumulating; the next megakernel draw waits for all of it (they share the spill slab)
+int draw_queued(DevFx* fx, DevTex* target, pt::TraceArgs& a, bool mesh, int gx, int gy)
+{
+    Dev* c = fx->ctx;
     const int persist = ((c->cu_count * 4 + pt::kShards - 1) / pt::kShards) * pt::kShards;
     if (c->backend == PT_BACKEND_WAVEFRONT) {
         // the quad-rounded frame is what gets shaded (helpers at odd edges included)
@@ -922,139 +837,101 @@ int render_trace(DevFx* fx, DevTex* target)
         a.spill = c->mk_spill;
         a.spill_stride = lanes;
     }
-    if (c->backend != PT_BACKEND_MEGAKERNEL || gy <= 0) {
-        // the wavefront / persistent schedules: on the main stream, their finish pass accumulating;
-        // the next megakernel draw waits for all of it (they share the spill slab)
-        if (c->backend != PT_BACKEND_MEGAKERNEL) c->need_fresh = true;
-        int rc = begin_draw(c, fx->prog);
-        if (rc) return rc;
-        if (gy > 0 && c->backend == PT_BACKEND_WAVEFRONT) {
-            HIPCHK(c, hipMemsetAsync(c->wf.cnt, 0, 16 * pt::kShards * sizeof(unsigned), c->stream));
-            HIPCHK(c, pt_launch_wavefront(fx->prog, c->counting ? 1 : 0, &a, &c->wf, gx, gy, persist, c->stream));
-        } else if (gy > 0) {
-            HIPCHK(c, pt_launch_persist(fx->prog, c->counting ? 1 : 0, &a, &c->gb, gx, n_wave_tiles, (unsigned)c->k.persist_tiles,
-                                        (unsigned)c->k.persist_refill, c->stream));
-            HIPCHK(c, pt_launch_finish(&a, &c->gb, gx, gy, c->stream));
-        }
-        return end_draw(c, fx->prog);
+    if (c->backend != PT_BACKEND_MEGAKERNEL) c->ov.need_fresh = true;
+    int rc = begin_draw(c, fx->prog);
+    if (rc) return rc;
+    if (gy > 0 && c->backend == PT_BACKEND_WAVEFRONT) {
+        HIPCHK(c, hipMemsetAsync(c->wf.cnt, 0, 16 * pt::kShards * sizeof(unsigned), c->stream));
+        HIPCHK(c, pt_launch_wavefront(fx->prog, c->counting ? 1 : 0, &a, &c->wf, gx, gy, persist, c->stream));
+    } else if (gy > 0 && c->backend == PT_BACKEND_PERSISTENT) {
+        HIPCHK(c, pt_launch_persist(fx->prog, c->counting ? 1 : 0, &a, &c->gb, gx, n_wave_tiles, (unsigned)c->k.persist_tiles,
+                                    (unsigned)c->k.persist_refill, c->stream));
+        HIPCHK(c, pt_launch_finish(&a, &c->gb, gx, gy, c->stream));
     }
+    return end_draw(c, fx->prog);
+}
 
-    // ---- the megakernel: draw k = mk_seq uses buffer set k % depth
-    // late-bounce compaction and the frames in flight (cont_decide): when compaction is on, no split
-    // tiles - their 16-lane waves would hand their slowest paths to pt_cont at once (r05j: dragon
-    // stand-in 4K with both 2222 Mpaths/s, with compaction alone 2762)
-    bool cont = false;
-    int depth = c->k.depth;
-    // a moving-camera draw that runs alone (PT_MOVING_SERIAL) does not compact: with no next frame beside it,
+// The megakernel draw over gx x gy tiles: plan (pt_plan.h), reserve, wait, launch, blend, defer the order build
+int draw_mega(DevFx* fx, DevTex* target, pt::TraceArgs& a, bool mesh, int gx, int gy)
+{
+    Dev* c = fx->ctx;
+    // ---- plan. Late-bounce compaction and the frames in flight first (cont_decide).
+    // A moving-camera draw that runs alone (PT_MOVING_SERIAL) does not compact: with no next frame beside it,
     // pt_cont's tail (a wave waits for its longest chain of walks) is the frame's (dragon stand-in 1080p
     // 1.19 -> 1.09 ms per frame, profiles/r06af_movpx.log); its slowest tiles are split instead. Nor is it a
     // draw of the auto trial, and pt_queue_stats reports it as not compacting.
     const bool alone = a.moving && c->k.moving_serial;
-    if (int rc = cont_decide(c, target, fx->prog, mesh && !c->counting && !PT_SECPROF_BUILD, alone, &cont, &depth)) return rc;
-    const size_t traced = (size_t)target->w * target->h / (size_t)std::max(1, c->num_parts);   // (about)
-    const int lag = draw_lag(c, traced);
-    if (depth != c->depth_run || lag != c->lag_run) {   // another buffer-set cycle: the draw waits for everything before it
-        c->depth_run = depth;
-        c->lag_run = lag;
-        c->need_fresh = true;
-    }
-    const unsigned nsets = (unsigned)(depth + lag);
-    const int par = (int)(c->mk_seq % nsets);            // buffer set
-    const int str = (int)(c->mk_seq % (unsigned)depth);  // stream and spill slab
-    // longest-first: the wave durations of draw k - sets (same buffer set) order this draw's workgroups
-    // when it drew the same grid, target and program; split tiles take 12 more workgroups each, in
-    // padding rows
-    const size_t n = (size_t)gx * gy;   // 16x16 tiles
-    const Dev::LptKey& key = c->lpt_key[par];
+    pt::ContTrial::Draw trial;
+    if (int rc = cont_decide(c, target, fx->prog, mesh && !c->counting && !PT_SECPROF_BUILD, alone, &trial)) return rc;
+    const bool cont = trial.on;
+    const int depth = trial.depth;
+    const size_t share = share_pixels(c, target);
+    const int lag = pt::draw_lag(c->k, share);
+    const pt::Overlap::Slot at = c->ov.slot(depth, lag);   // draw k = mk_seq: buffer set k % (depth + lag), stream k % depth
+    // longest-first: the costs of draw k - sets (same buffer set) order this one if it drew the same thing
+    const Dev::LptKey& key = c->lpt_key[at.set];
     const bool lpt = c->k.lpt && !c->counting;
-    const bool same = lpt && key.valid && key.n == n && key.target == target && key.prog == fx->prog &&
-                      key.part == c->part && key.parts == c->num_parts && c->lpt_cap >= n;
-    const unsigned split_cap = (unsigned)std::min<size_t>(c->k.split_tiles, n) & ~7u;
-    const unsigned split = same && !cont ? split_cap : 0u;
-    const unsigned extra = 4u * pt::kSplitParts - 4u;   // more workgroups per split tile
-    const int gy_grid = gy + (int)((extra * split + 4u * gx - 1) / (4u * gx));
-    if (mesh) {
-        const size_t lanes = (size_t)gx * gy_grid * pt::kBlock;
-        if (lanes * kSpillPerLane > 0xffffffffull)   // 32-bit slab index
-            return fail(c, PT_ERR_ARG, "render target too large for the BVH stack slab");
-        int rc = spill_reserve(c, lanes);
-        if (rc) return rc;
-        a.spill = spill_slab(c, str);
-        a.spill_stride = lanes;
-    }
-    if (int rc = rad_reserve(c, (size_t)target->w * target->h)) return rc;
-    a.rad = c->rad_mem + (size_t)par * c->rad_pixels;
-    if (cont) {   // (records for this draw's set: allocated by cont_decide already, unless the lag changed)
-        if (int rc = cont_reserve(c, traced_pixels(c, target), (int)nsets)) return rc;
-        cont_args(c, par, a);
-    }
-    if (lpt && c->lpt_cap < n) {
-        if (c->lpt_mem) {   // (pt_trace on the side streams reads the order and writes the costs: every stream first)
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            for (int p = 0; p < Dev::kDepthMax; p++)
-                if (c->ts[p]) HIPCHK(c, hipStreamSynchronize(c->ts[p]));
-            HIPCHK(c, hipFree(c->lpt_mem));
-            c->lpt_mem = nullptr;
-        }
-        HIPCHK(c, hipMalloc(&c->lpt_mem, (5 * n + 1) * Dev::kSetsMax * sizeof(unsigned)));   // cost | order | split
-        c->lpt_cap = n;
-        c->need_fresh = true;
-        for (auto& k : c->lpt_key) k.valid = false;
-    }
-    // where the path tracing runs: a side stream gated by the main stream's state when the previous
-    // megakernel draw began (or now: the first draw, after another schedule or a stream switch, with
-    // counting kernels, or when a sampler is a render target, which draws on the main stream may write)
-    bool overlap = c->k.overlap && !c->counting && !PT_SECPROF_BUILD;   // (experiment builds: one wave log)
-    if (a.moving && c->k.moving_serial) overlap = false;
+    const bool same = lpt && key.valid && key.n == (size_t)gx * gy && key.target == target && key.prog == fx->prog &&
+                      key.part == c->part && key.parts == c->num_parts && c->lpt_cap >= key.n;
+    const pt::MegaGrid g(gx, gy, same, cont, c->k);
+    // where the path tracing runs: a side stream gated by the main stream's state when an earlier megakernel
+    // draw began (or now: the first draw, after another schedule or a stream switch, with counting kernels, or
+    // when a sampler is a render target, which draws on the main stream may write)
+    bool overlap = c->k.overlap && !c->counting && !PT_SECPROF_BUILD && !alone;   // (experiment builds: one wave log)
     for (const auto& kv : fx->samplers)
         if (kv.second && kv.second->kind == TEX_RT && kv.first != "previousBuffer") overlap = false;
+
+    // ---- reserve (new memory makes the draw wait for everything before it: slab_grow)
+    if (mesh) {
+        if (g.lanes * kSpillPerLane > 0xffffffffull)   // 32-bit slab index
+            return fail(c, PT_ERR_ARG, "render target too large for the BVH stack slab");
+        if (int rc = spill_reserve(c, g.lanes)) return rc;
+        a.spill = spill_slab(c, at.stream);
+        a.spill_stride = g.lanes;
+    }
+    if (int rc = rad_reserve(c, (size_t)target->w * target->h)) return rc;
+    a.rad = c->rad_mem + (size_t)at.set * c->rad_pixels;
+    if (cont) {   // (records for this draw's set: allocated by cont_decide already, unless the lag changed)
+        if (int rc = cont_reserve(c, owned_pixels(c, target), depth + lag)) return rc;
+        // (the record sort's keys take the model's root box: child-pair walks only)
+        cont_args(c, at.set, c->k.cont_sort && a.bvh_walk != pt::WALK_REF, a);
+    }
+    if (lpt && c->lpt_cap < g.n) {   // cost | order | split; pt_trace on the side streams reads the order and writes the costs
+        if (int rc = slab_grow(c, c->lpt_mem, c->lpt_cap, g.n, (5 * g.n + 1) * Dev::kSetsMax * sizeof(unsigned), WAIT_ALL, true))
+            return rc;
+        for (auto& k : c->lpt_key) k.valid = false;
+    }
+
+    // ---- wait: the main stream's mark for this draw, and the mark pt::Overlap picks for its path tracing
     hipStream_t ts = c->stream;
-    if (overlap) {
+    if (overlap)
         if (int rc = overlap_init(c)) return rc;
-        const unsigned k = c->mk_seq, D = nsets;
-        if (c->need_fresh) { c->mark_floor = k; c->need_fresh = false; }
-        HIPCHK(c, hipEventRecord(c->ev_mark[par], c->stream));
-        ts = c->ts[str];
-        // the mark of draw k - sets + 1 (its state: draw k - sets' blend, order build and output), or
-        // of the oldest draw after everything this draw must wait for; the draw k - depth before it on
-        // this stream is ordered by the stream
-        const unsigned w = k + 1 >= D ? std::max(k + 1 - D, c->mark_floor) : c->mark_floor;
-        HIPCHK(c, hipStreamWaitEvent(ts, c->ev_mark[w % D], 0));
-    } else {
-        c->need_fresh = true;
+    const int wait = c->ov.step(depth, lag, overlap).wait;
+    if (overlap) {
+        HIPCHK(c, hipEventRecord(c->ev_mark[at.set], c->stream));
+        ts = c->ts[at.stream];
+        HIPCHK(c, hipStreamWaitEvent(ts, c->ev_mark[wait], 0));
     }
+
+    // ---- launch, on `ts`
     if (lpt) {
-        if (!same) HIPCHK(c, hipMemsetAsync(c->lpt_cost(par), 0, 4 * n * sizeof(unsigned), ts));   // costs start afresh
-        a.order = same ? c->lpt_order(par) : nullptr;
-        a.cost = c->lpt_cost(par);
-        // from both ends (runs of 8 tiles: the slowest, the cheapest, ...) also for compacting draws whose order
-        // is not flattened: with the slowest tiles' late bounces handed to pt_cont, cheap tiles mixed in early
-        // keep the slots full (dragon stand-in 1080p +1.5 %, its 20-frame run +1.7 %, helmet +1.6 %, three
-        // rounds, profiles/r06bo_*; uncompacted the bunny lost 1.4 %, and at 4K the flattened order 1.9 %)
-        a.order_zig = c->k.lpt_zig || (cont && c->k.zig_cont && n <= (size_t)c->k.lpt_flat_tiles) ? 1u : 0u;
-        a.split = (a.order && split) ? c->lpt_split(par) : nullptr;
+        if (!same) HIPCHK(c, hipMemsetAsync(c->lpt_cost(at.set), 0, 4 * g.n * sizeof(unsigned), ts));   // costs start afresh
+        a.order = same ? c->lpt_order(at.set) : nullptr;
+        a.cost = c->lpt_cost(at.set);
+        a.order_zig = g.order_zig;
+        a.split = (a.order && g.split) ? c->lpt_split(at.set) : nullptr;
     }
-    a.ntiles = (unsigned)n;
+    a.ntiles = (unsigned)g.n;
     if (int rc = begin_draw(c, fx->prog, ts)) return rc;
-    if (cont && c->k.cont_sort && a.bvh_walk != pt::WALK_REF) {   // (the model's root box: child-pair walks only)
-        const size_t cap = c->cont_cap;
-        auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-        char* m = (char*)a.cont_rec + cap * 64 + al(cap * 4);
-        a.cont_perm = (unsigned*)m;
-        a.cont_rank = (unsigned*)(m + al(cap * 4));
-        a.cont_key = (unsigned short*)(m + 2 * al(cap * 4));
-        a.cont_bins = (unsigned*)(m + 2 * al(cap * 4) + al(cap * 2));
-        // 8x8x8 cells for draws that trace 3 Mpx or more (4K: dragon stand-in +0.4 %, helmet +1.1 %, sky +
-        // dragon +0.6 %, three rounds, profiles/r06bj_*; at 1080p the helmet lost 5.5 % with them, r06ao_*)
-        const unsigned gb = c->k.cont_grid_env || traced < (size_t)c->k.cont_big_pixels ? (unsigned)c->k.cont_grid_bits : 3u;
+    if (a.cont_bins) {   // (PT_CONT_SORT) the key's origin cells over the model's root box
+        a.cont_grid_bits = pt::MegaGrid::sort_grid_bits(c->k, share);
         for (int k = 0; k < 3; k++) {
             const float ext = a.bvh_root_box[3 + k] - a.bvh_root_box[k];
-            a.cont_cell[k] = ext > 0.0f ? (float)(1u << gb) / ext : 0.0f;
+            a.cont_cell[k] = ext > 0.0f ? (float)(1u << a.cont_grid_bits) / ext : 0.0f;
         }
-        a.cont_grid_bits = gb;
     }
-    HIPCHK(c, pt_launch_trace(fx->prog, c->counting ? 1 : 0, &a, gx, a.split ? gy_grid : gy, ts));
-    if (a.cont_bins) {   // (PT_CONT_SORT) the records' order, from the keys' totals and ranks pt_trace took
+    HIPCHK(c, pt_launch_trace(fx->prog, c->counting ? 1 : 0, &a, gx, a.split ? g.gy_grid : gy, ts));
+    if (a.cont_bins) {   // ... and the records' order, from the keys' totals and ranks pt_trace took
         pt::SortArgs so;
         std::memset(&so, 0, sizeof(so));
         so.count = a.cont_count;
@@ -1066,39 +943,50 @@ int render_trace(DevFx* fx, DevTex* target)
         HIPCHK(c, pt_launch_cont_sort(&so, c->cont_cap, ts));
     }
     if (cont) {   // (its one-wave workgroups index the spill slab below the trace grid's lanes)
-        // (the sky composite keeps 2048: its sky pixels store few records, and 1024 waves cost it 0.5 %)
-        const bool big = !c->k.cont_waves_env && traced >= (size_t)c->k.cont_big_pixels && fx->prog != PT_PROG_SKY_MESH;
-        HIPCHK(c, pt_launch_cont(fx->prog, &a, (int)std::min<size_t>(big ? c->k.cont_waves_big : c->k.cont_waves, (size_t)gx * gy * 4), ts));
+        HIPCHK(c, pt_launch_cont(fx->prog, &a, g.cont_waves(c->k, share, fx->prog == PT_PROG_SKY_MESH), ts));
         c->cont_draws++;
     }
     // the draw's timing events bracket all of its path tracing on the side stream: pt_trace and, when the
     // draw compacts, pt_cont (the blend below is the main stream's)
     if (int rc = end_draw(c, fx->prog, ts)) return rc;
     if (overlap) {
-        HIPCHK(c, hipEventRecord(c->ev_traced[str], ts));
-        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_traced[str], 0));
+        HIPCHK(c, hipEventRecord(c->ev_traced[at.stream], ts));
+        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_traced[at.stream], 0));
     }
-    // the history half of main() on the main stream, where the copy / output draws that read the
+
+    // ---- blend: the history half of main() on the main stream, where the copy / output draws that read the
     // accumulation follow
     pt::BlendArgs b{ a.width, a.height, a.num_parts, a.part, a.frame, a.moving, a.rad, a.prev, a.out, a.cont_count, a.cont_bins };
-    // (one-wave workgroups up to 8192 tiles, as the output pass below)
-    HIPCHK(c, pt_launch_blend(&b, gy, c->stream, n <= pt::kOrderHeld * 64u ? c->k.main_waves : 0));
-    if (a.cost) {   // this draw's costs order draw k + 2: the build rides along with the next screenOutput
-        c->pending_order = { (unsigned)n, a.cost, c->lpt_order(par), c->lpt_split(par), split_cap,
+    HIPCHK(c, pt_launch_blend(&b, gy, c->stream, g.one_wave ? c->k.main_waves : 0));
+
+    // ---- this draw's costs order draw k + sets: the build rides along with the next screenOutput
+    if (a.cost) {
+        c->pending_order = { (unsigned)g.n, a.cost, c->lpt_order(at.set), c->lpt_split(at.set), g.split_cap,
                              (unsigned)c->k.split_dominance, c->k.split_near, c->k.lpt_flat, (unsigned)c->k.lpt_flat_tiles };
         c->order_pending = true;
         if (!c->k.fuse_order) { if (int rc = flush_order(c)) return rc; }
-        c->lpt_key[par] = { true, n, target, fx->prog, c->part, c->num_parts };
+        c->lpt_key[at.set] = { true, g.n, target, fx->prog, c->part, c->num_parts };
     }
-    c->mk_seq++;
+    c->ov.mk_seq++;
     return PT_OK;
+}
+
+int render_trace(DevFx* fx, DevTex* target)
+{
+    Dev* c = fx->ctx;
+    if (int rc = flush_order(c)) return rc;   // the last draw's order (before lpt_mem could be reallocated)
+    pt::TraceArgs a;
+    bool mesh = false;
+    if (int rc = trace_args(fx, target, a, mesh)) return rc;
+    const int gx = (target->w + pt::kTile - 1) / pt::kTile, gy = bands_owned(c, target->h);
+    return c->backend == PT_BACKEND_MEGAKERNEL && gy > 0 ? draw_mega(fx, target, a, mesh, gx, gy)
+                                                         : draw_queued(fx, target, a, mesh, gx, gy);
 }
 
 int launch_copy(Dev* c, DevTex* src, DevTex* dst, int num_parts, int part)
 {
     pt::CopyArgs a{ dst->w, dst->h, num_parts, part, (const float4*)src->d, (float4*)dst->d };
-    const int nb = (dst->h + pt::kTile - 1) / pt::kTile;
-    int gx = (dst->w + 255) / 256, gy = part < nb ? (nb - part + num_parts - 1) / num_parts : 0;
+    const int gx = (dst->w + 255) / 256, gy = pt::bands_owned(dst->h, num_parts, part);
     if (gy > 0) HIPCHK(c, pt_launch_copy(&a, gx, gy, c->stream));
     return PT_OK;
 }
@@ -1175,8 +1063,7 @@ int render_output(DevFx* fx, DevTex* target)
         }
         // one-wave workgroups while a fused order build fits one wave's registers (<= 8192 tiles: up to
         // ~2 MP, and a rank's share of 4K), else the 4-wave blocks with a 256-thread order build
-        const int nb = (a.height + 15) / 16, ob = a.part < nb ? (nb - a.part + a.num_parts - 1) / a.num_parts : 0;
-        const unsigned tiles = (unsigned)((a.width + 15) / 16) * (unsigned)ob;   // (as pt_launch_output's grid)
+        const unsigned tiles = (unsigned)((a.width + 15) / 16) * (unsigned)pt::bands_owned(a.height, a.num_parts, a.part);   // (as pt_launch_output's grid)
         const bool one = std::max(tiles, a.ob.ntiles) <= pt::kOrderHeld * 64u;   // (ob.ntiles 0: no order build)
         HIPCHK(c, pt_launch_output(&a, c->stream, one ? c->k.main_waves : 0));
     }
@@ -1250,7 +1137,7 @@ Dev* dev_ctx_create(int device, int* err)
     c->device = device;
     c->cu_count = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     pt::read_knobs(c->k);
-    c->depth_run = c->k.depth;
+    c->ov.depth_run = c->k.depth;
     c->bvh_layout = c->k.bvh_layout;
     c->draw_events = c->k.draw_events != 0;
     hipError_t e = hipSetDevice(device);
@@ -1320,7 +1207,7 @@ int dev_sync(Dev* c)
     if (flags) {   // (on the main stream, which the next draw's path tracing waits for: not the null stream)
         HIPCHK(c, hipMemsetAsync(c->d_err, 0, sizeof(unsigned), c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->need_fresh = true;
+        c->ov.need_fresh = true;
         if (flags & pt::E_STACK) return fail(c, PT_ERR_DATA, "BVH traversal needed more than stackLevels[28]");
     }
     return PT_OK;
@@ -1557,7 +1444,7 @@ int dev_set_stream(Dev* c, void* stream)
     if (int rc = flush_order(c)) return rc;        // on the stream its draw ran on
     HIPCHK(c, hipStreamSynchronize(c->stream));   // work already queued finishes first
     c->stream = stream ? (hipStream_t)stream : c->own_stream;
-    c->need_fresh = true;   // the next megakernel draw waits for the new stream's state
+    c->ov.need_fresh = true;   // the next megakernel draw waits for the new stream's state
     return PT_OK;
 }
 
@@ -1687,16 +1574,16 @@ int dev_queue_stats(Dev* c, uint32_t out[16])
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = flush_order(c)) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    const int p = (int)(c->mk_seq % (unsigned)(c->depth_run + c->lag_run));   // the tiles the next megakernel draw of the same grid splits
+    const int p = c->ov.next().set;   // the tiles the next megakernel draw of the same grid splits
     if (c->lpt_mem && c->lpt_key[p].valid)
         HIPCHK(c, hipMemcpy(&out[7], c->lpt_split(p), sizeof(uint32_t), hipMemcpyDeviceToHost));
     // late-bounce compaction of the last megakernel draw: 0 off, 1 auto decided off, 2 auto decided on,
     // 3 forced on (PT_CONT=1), 4 auto trial, 5 / 6 default on / off; bits 8-15: its frames in flight;
     // bits 16-31: the draws that launched pt_cont so far (mod 2^16);
     // out[15]: the auto trial's ms with it on per ms without (the faster depth), x 1000
-    out[14] = (uint32_t)c->cont_last | (uint32_t)c->depth_run << 8 | (c->cont_draws & 0xffffu) << 16;
-    const float off = std::min(c->tune.ms_off, c->tune.ms_off2);
-    out[15] = (c->cont_last == 1 || c->cont_last == 2) && off > 0.0f ? (uint32_t)(1000.0f * c->tune.ms_on / off) : 0u;
+    out[14] = (uint32_t)c->cont_last | (uint32_t)c->ov.depth_run << 8 | (c->cont_draws & 0xffffu) << 16;
+    const float off = std::min(c->trial.ms_off, c->trial.ms_off2);
+    out[15] = (c->cont_last == 1 || c->cont_last == 2) && off > 0.0f ? (uint32_t)(1000.0f * c->trial.ms_on / off) : 0u;
     if (!c->wf_mem) return PT_OK;
     std::vector<unsigned> h(16 * pt::kShards);
     HIPCHK(c, hipMemcpy(h.data(), c->wf.cnt, h.size() * sizeof(unsigned), hipMemcpyDeviceToHost));

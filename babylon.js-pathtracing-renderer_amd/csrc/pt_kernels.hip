@@ -819,8 +819,7 @@ hipError_t pt_launch_copy(const pt::CopyArgs* a, int grid_x, int grid_y, hipStre
 
 hipError_t pt_launch_output(const pt::OutputArgs* a, hipStream_t s, int waves)
 {
-    const int nb = (a->height + 15) / 16;
-    dim3 grid((a->width + 15) / 16, a->part < nb ? (nb - a->part + a->num_parts - 1) / a->num_parts : 0);
+    dim3 grid((a->width + 15) / 16, pt::bands_owned(a->height, a->num_parts, a->part));
     if (grid.y == 0) {   // no band of this part: a fused order build runs on its own
         if (a->ob.cost) return pt_launch_order_build(&a->ob, s);
         return hipGetLastError();
