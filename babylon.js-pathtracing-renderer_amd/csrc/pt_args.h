@@ -163,6 +163,11 @@ struct TraceArgs {
     const unsigned* split;
     unsigned ntiles;       // 16x16 tiles of the draw
     Tex8 albedo, bump, metal, emissive;
+    // feature buffers (pt_set_feature_targets): the pixel's final G-buffer, staged per pixel (py * width + px)
+    // for pt_feature_fold - feat0 = objectNormal.xyz, objectID; feat1 = objectColor.xyz, 0. Written by the
+    // FEAT variants of pt_trace and, tested at run time, by the counting ones (NULL: no features)
+    float4* feat0;
+    float4* feat1;
     // diagnostics
     unsigned long long* counters;   // C_NUM entries, only with counting builds
     unsigned* err;                  // ErrBits
@@ -248,6 +253,22 @@ struct BlendArgs {
     unsigned* cont_count;   // late-bounce compaction: the draw's record counter, added to the buffer set's 64-bit
                             // total at [2..3] (pt_cont_stats) and zeroed here (NULL: none)
     unsigned* cont_bins;    // (PT_CONT_SORT) the record sort's kSortBins totals, zeroed here (NULL: none)
+};
+
+// pt_feature_fold: a draw's G-buffer sample folded into the effect's feature targets in place, over the owned
+// 16-row bands, by the beauty's history rule (include/pt.h pt_set_feature_targets). g0 / g1: the staged sample
+// (normal.xyz, id | colour.xyz, -), `stride` pixels per row: the megakernel's staging slab (the target's
+// width) or the queued backends' per-pixel G-buffer (WfBufs::gb0 / gb1, the quad-rounded width)
+struct FoldArgs {
+    int width, height;
+    int num_parts, part;
+    float frame;
+    int moving;
+    const float4* g0;
+    const float4* g1;
+    int stride;
+    float4* normal_id;       // NULL: not produced
+    float4* albedo_weight;   // NULL: not produced
 };
 
 // (PT_CONT_SORT) pt_cont's records ordered by a ray key (pt_kernels.hip pt_cont_hist / pt_cont_scatter)

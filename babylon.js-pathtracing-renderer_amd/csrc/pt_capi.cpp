@@ -11,9 +11,10 @@
 //                      late-bounce compaction the record sort and pt_cont, on one of the side streams,
 //                      up to `depth` frames in flight, each gated by a mark on the main stream; then
 //                      pt_blend on the main stream, and the longest-first order build deferred into the
-//                      next screenOutput. Which buffer set, stream and mark, the grid and whether the
-//                      draw compacts is pt_plan.h's arithmetic; this file reserves memory and issues
-//                      the HIP calls. The wavefront and persistent schedules (draw_queued) run on the
+//                      next screenOutput; with feature targets bound (dev_set_feature_targets) pt_trace also
+//                      stages its G-buffer and pt_feature_fold follows the blend. Which buffer set, stream
+//                      and mark, the grid and whether the draw compacts is pt_plan.h's arithmetic; this
+//                      file reserves memory and issues the HIP calls. The wavefront and persistent schedules (draw_queued) run on the
 //                      main stream alone;
 //   SCREEN_COPY     -> pt_copy over the owned bands, deferred to fuse with the next screenOutput;
 //   SCREEN_OUTPUT   -> pt_output into the canvas (RGBA8) or an RGBA32F target, with a deferred copy
@@ -45,6 +46,7 @@ hipError_t pt_launch_trace(int prog, int count, const pt::TraceArgs* a, int grid
 hipError_t pt_launch_order_build(const pt::OrderArgs* a, hipStream_t s);
 hipError_t pt_launch_copy(const pt::CopyArgs* a, int grid_x, int grid_y, hipStream_t s);
 hipError_t pt_launch_blend(const pt::BlendArgs* a, int bands, hipStream_t s, int waves);
+hipError_t pt_launch_feature_fold(const pt::FoldArgs* a, int bands, hipStream_t s, int waves);
 hipError_t pt_launch_cont_sort(const pt::SortArgs* a, size_t cap, hipStream_t s);
 hipError_t pt_launch_cont(int prog, const pt::TraceArgs* a, int waves, hipStream_t s);
 hipError_t pt_launch_output(const pt::OutputArgs* a, hipStream_t s, int waves);
@@ -113,6 +115,7 @@ struct DevFx {
     int prog = PT_PROG_UNKNOWN;
     std::unordered_map<std::string, Uniform> uniforms;
     std::unordered_map<std::string, DevTex*> samplers;
+    DevTex* feat[2] = {};   // feature targets (dev_set_feature_targets): normal + id, albedo + weight
 };
 
 struct Dev {
@@ -166,6 +169,10 @@ struct Dev {
     pt::Overlap ov;               // which draw this is, its buffer set, stream and mark (pt_plan.h)
     float4* rad_mem = nullptr;    // rad[sets()]: radiance + flag per pixel
     size_t rad_pixels = 0;
+    // feature buffers: feat[sets()][2] planes of a float4 per pixel beside rad (the G-buffer pt_trace stages for
+    // pt_feature_fold), allocated once a draw has feature targets bound
+    float4* feat_mem = nullptr;
+    size_t feat_pixels = 0;
     // late-bounce compaction of the megakernel's mesh draws (pt_trace<P,false,true> -> pt_cont; k.cont_mode):
     // per buffer set 64-B path records, their pixels and a counter
     void* cont_mem = nullptr;
@@ -494,6 +501,13 @@ int rad_reserve(Dev* c, size_t pixels)
     return slab_grow(c, c->rad_mem, c->rad_pixels, pixels, (size_t)c->sets() * pixels * sizeof(float4), WAIT_MAIN, true);
 }
 
+// feat[sets()][2] (pt_trace -> pt_feature_fold) for a frame of `pixels`: same sets, same growth rule as rad
+int feat_reserve(Dev* c, size_t pixels)
+{
+    if (pixels <= c->feat_pixels) return PT_OK;
+    return slab_grow(c, c->feat_mem, c->feat_pixels, pixels, (size_t)c->sets() * 2 * pixels * sizeof(float4), WAIT_MAIN, true);
+}
+
 // the pixels a draw of `target` traces: the owned bands, a bound on its records, and about, for the measured
 // thresholds (pt_plan.h: the two are not interchangeable)
 size_t owned_pixels(const Dev* c, const DevTex* target) { return pt::owned_pixels(target->w, target->h, c->num_parts, c->part); }
@@ -814,6 +828,31 @@ int trace_args(DevFx* fx, DevTex* target, pt::TraceArgs& a, bool& mesh)
     return PT_OK;
 }
 
+// The feature targets of a draw of `target`, checked (pt_set_feature_targets)
+int feature_check(const DevFx* fx, const DevTex* target)
+{
+    Dev* c = fx->ctx;
+    const DevTex* prev = sampler(fx, "previousBuffer");
+    for (int k = 0; k < 2; k++) {
+        const DevTex* t = fx->feat[k];
+        if (!t) continue;
+        if (t->w != target->w || t->h != target->h)
+            return fail(c, PT_ERR_STATE, "a feature target must have the draw target's size");
+        if (t == target || t->d == target->d || (prev && (t == prev || t->d == prev->d)))
+            return fail(c, PT_ERR_STATE, "a feature target must not be the draw target or previousBuffer");
+    }
+    if (fx->feat[0] && fx->feat[1] && (fx->feat[0] == fx->feat[1] || fx->feat[0]->d == fx->feat[1]->d))
+        return fail(c, PT_ERR_STATE, "the two feature targets must be distinct");
+    return PT_OK;
+}
+
+// the feature fold of a draw, from the G-buffer staged at g0 / g1 (`stride` pixels per row)
+pt::FoldArgs fold_args(const DevFx* fx, const pt::TraceArgs& a, const float4* g0, const float4* g1, int stride)
+{
+    return pt::FoldArgs{ a.width, a.height, a.num_parts, a.part, a.frame, a.moving, g0, g1, stride,
+                         fx->feat[0] ? (float4*)fx->feat[0]->d : nullptr, fx->feat[1] ? (float4*)fx->feat[1]->d : nullptr };
+}
+
 // The wavefront / persistent schedules (and a draw that owns no band) over gx x gy tiles: on the main stream,
 // their finish pass accumulating; the next megakernel draw waits for all of it (they share the spill slab)
 int draw_queued(DevFx* fx, DevTex* target, pt::TraceArgs& a, bool mesh, int gx, int gy)
@@ -848,7 +887,14 @@ int draw_queued(DevFx* fx, DevTex* target, pt::TraceArgs& a, bool mesh, int gx, 
                                     (unsigned)c->k.persist_refill, c->stream));
         HIPCHK(c, pt_launch_finish(&a, &c->gb, gx, gy, c->stream));
     }
-    return end_draw(c, fx->prog);
+    if (int erc = end_draw(c, fx->prog)) return erc;
+    // feature targets: folded from the backend's per-pixel G-buffer (quad-rounded rows), after its finish pass
+    if (gy > 0 && c->backend != PT_BACKEND_MEGAKERNEL && (fx->feat[0] || fx->feat[1])) {
+        const pt::WfBufs& w = c->backend == PT_BACKEND_WAVEFRONT ? c->wf : c->gb;
+        const pt::FoldArgs f = fold_args(fx, a, w.gb0, w.gb1, w.wq);
+        HIPCHK(c, pt_launch_feature_fold(&f, gy, c->stream, 0));
+    }
+    return PT_OK;
 }
 
 // The megakernel draw over gx x gy tiles: plan (pt_plan.h), reserve, wait, launch, blend, defer the order build
@@ -891,6 +937,12 @@ int draw_mega(DevFx* fx, DevTex* target, pt::TraceArgs& a, bool mesh, int gx, in
     }
     if (int rc = rad_reserve(c, (size_t)target->w * target->h)) return rc;
     a.rad = c->rad_mem + (size_t)at.set * c->rad_pixels;
+    const bool feat = fx->feat[0] || fx->feat[1];
+    if (feat) {   // the set's staged G-buffer: two planes
+        if (int rc = feat_reserve(c, (size_t)target->w * target->h)) return rc;
+        a.feat0 = c->feat_mem + (size_t)at.set * 2 * c->feat_pixels;
+        a.feat1 = a.feat0 + c->feat_pixels;
+    }
     if (cont) {   // (records for this draw's set: allocated by cont_decide already, unless the lag changed)
         if (int rc = cont_reserve(c, owned_pixels(c, target), depth + lag)) return rc;
         // (the record sort's keys take the model's root box: child-pair walks only)
@@ -958,6 +1010,11 @@ int draw_mega(DevFx* fx, DevTex* target, pt::TraceArgs& a, bool mesh, int gx, in
     // accumulation follow
     pt::BlendArgs b{ a.width, a.height, a.num_parts, a.part, a.frame, a.moving, a.rad, a.prev, a.out, a.cont_count, a.cont_bins };
     HIPCHK(c, pt_launch_blend(&b, gy, c->stream, g.one_wave ? c->k.main_waves : 0));
+    // ---- feature targets: the staged G-buffer folded right after, on the main stream too, so folds keep the draws' order
+    if (feat) {
+        const pt::FoldArgs f = fold_args(fx, a, a.feat0, a.feat1, a.width);
+        HIPCHK(c, pt_launch_feature_fold(&f, gy, c->stream, g.one_wave ? c->k.main_waves : 0));
+    }
 
     // ---- this draw's costs order draw k + sets: the build rides along with the next screenOutput
     if (a.cost) {
@@ -978,6 +1035,7 @@ int render_trace(DevFx* fx, DevTex* target)
     pt::TraceArgs a;
     bool mesh = false;
     if (int rc = trace_args(fx, target, a, mesh)) return rc;
+    if (int rc = feature_check(fx, target)) return rc;
     const int gx = (target->w + pt::kTile - 1) / pt::kTile, gy = bands_owned(c, target->h);
     return c->backend == PT_BACKEND_MEGAKERNEL && gy > 0 ? draw_mega(fx, target, a, mesh, gx, gy)
                                                          : draw_queued(fx, target, a, mesh, gx, gy);
@@ -1179,6 +1237,7 @@ void dev_ctx_destroy(Dev* c)
     if (c->lpt_mem) hipFree(c->lpt_mem);
     if (c->mk_spill) hipFree(c->mk_spill);
     if (c->rad_mem) hipFree(c->rad_mem);
+    if (c->feat_mem) hipFree(c->feat_mem);
     if (c->cont_mem) hipFree(c->cont_mem);
     for (auto& e : c->tune_ev) if (e) hipEventDestroy(e);
     for (int p = 0; p < Dev::kSetsMax; p++)
@@ -1381,6 +1440,9 @@ void dev_texture_destroy(DevTex* t)
     for (auto* fx : c->effects)
         for (auto& kv : fx->samplers)
             if (kv.second == t) kv.second = nullptr;
+    for (auto* fx : c->effects)   // a bound feature target: unbound (the folds queued so far are waited for below)
+        for (auto& f : fx->feat)
+            if (f == t) f = nullptr;
     if (t->d && !t->external) { hipStreamSynchronize(c->stream); hipFree(t->d); }
     if (t->pairs_mem) { hipStreamSynchronize(c->stream); hipFree(t->pairs_mem); }
     for (auto* o : c->textures)   // records built against this triangle texture are stale
@@ -1605,6 +1667,20 @@ int dev_cont_stats(Dev* c, uint64_t out[2])
     if (int rc = cont_totals(c, &stored)) return rc;
     out[0] = c->cont_stored + stored;
     out[1] = c->cont_draws;
+    return PT_OK;
+}
+
+int dev_set_feature_targets(DevFx* fx, DevTex* normal_id, DevTex* albedo_weight)
+{
+    if (!fx) return PT_ERR_ARG;
+    Dev* c = fx->ctx;
+    if (fx->prog == PT_PROG_SCREEN_COPY || fx->prog == PT_PROG_SCREEN_OUTPUT)
+        return fail(c, PT_ERR_ARG, "feature targets need a path-tracing effect");
+    for (DevTex* t : { normal_id, albedo_weight })
+        if (t && (t->ctx != c || t->kind != TEX_RT))
+            return fail(c, PT_ERR_ARG, "a feature target must be a render target of this context");
+    fx->feat[0] = normal_id;
+    fx->feat[1] = albedo_weight;
     return PT_OK;
 }
 

@@ -52,6 +52,7 @@ int dev_reset_counters(Dev* c);
 int dev_timing_latency(Dev* c, int prog, float* ms, int cap, int* n);
 int dev_queue_stats(Dev* c, uint32_t out[16]);
 int dev_cont_stats(Dev* c, uint64_t out[2]);
+int dev_set_feature_targets(DevFx* fx, DevTex* normal_id, DevTex* albedo_weight);
 int dev_math_exhaustive(Dev* c, int op, uint64_t* mismatches);
 int dev_math_probe(Dev* c, int op, const float* x, const float* y, float* out, int n);
 

@@ -713,6 +713,22 @@ int pt_cont_stats(pt_ctx* c, uint64_t out[2])
     return PT_OK;
 }
 
+int pt_set_feature_targets(pt_effect* fx, pt_texture* normal_id, pt_texture* albedo_weight)
+{
+    if (!fx) return PT_ERR_ARG;
+    pt_ctx* c = fx->ctx;
+    if (!is_trace(fx->prog)) return fail(c, PT_ERR_ARG, "feature targets need a path-tracing effect");
+    for (pt_texture* t : { normal_id, albedo_weight })
+        if (t && (t->ctx != c || t->kind != K_RT))
+            return fail(c, PT_ERR_ARG, "a feature target must be a render target of this context");
+    // every part folds its own bands into its share of the targets (distributed by bands like any render target)
+    for (size_t k = 0; k < fx->sub.size(); k++)
+        if (int rc = take(c, (int)k, dev_set_feature_targets(fx->sub[k], normal_id ? normal_id->sub[k] : nullptr,
+                                                             albedo_weight ? albedo_weight->sub[k] : nullptr)))
+            return rc;
+    return PT_OK;
+}
+
 int pt_math_probe(pt_ctx* c, int op, const float* x, const float* y, float* out, int n)
 {
     if (!c) return PT_ERR_ARG;

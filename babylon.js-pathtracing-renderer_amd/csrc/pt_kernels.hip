@@ -4,6 +4,8 @@
 //                         with the Cornell / glTF scene shaders' SetupScene, SceneIntersect and
 //                         CalculateRadiance). One lane = one pixel = one path of <= 6 segments.
 //   pt_copy               screenCopy (js/PathTracingCommon.js:1-16), band-aware.
+//   pt_feature_fold       a draw's G-buffer sample folded into the bound feature targets (normal + id,
+//                         albedo + weight) by the accumulation's history rule.
 //   pt_output             screenOutput (js/PathTracingCommon.js:19-309): 5x5 / 3x3 edge-aware
 //                         filter, 1/N, Reinhard, gamma 0.4545, unorm8.
 //   pt_math_probe_kernel  device self-test of the pinned built-ins.
@@ -257,6 +259,59 @@ __global__ __launch_bounds__(64) void pt_blend_w(BlendArgs a, int units_x, int u
         const int band = (rest >> 2) * a.num_parts + a.part;
         const int x = cx * 64 + threadIdx.x;
         if (x < a.width) blendRows(a, x, band * kTile + (rest & 3));
+    }
+}
+
+// ------------------------------------------------------------------------------ feature buffers
+// A draw's G-buffer sample folded into the effect's feature targets (pt_set_feature_targets), in place, by
+// the rule of the accumulation above: history 0 at frame 1 (+0.0, still added), history and sample halved
+// while the camera moves. One IEEE multiply per product and one add per component (-ffp-contract=off).
+// normal_id.w is this draw's objectID, albedo_weight.w the weight of the samples held. Four rows of a band
+// per thread as blendRows; every access is 16 B per lane, coalesced along the row; loads first.
+PT_D void foldRows(const FoldArgs& a, int x, int r0)
+{
+    typedef float nt4 __attribute__((ext_vector_type(4)));
+    const bool reset = a.frame == 1.0f;
+    const float f = (!reset && a.moving) ? 0.5f : 1.0f;
+    nt4 g0[4], g1[4], on[4], oa[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int y = r0 + 4 * k;
+        if (y < a.height) {
+            const long long j = (long long)y * a.stride + x, i = (long long)y * a.width + x;
+            g0[k] = __builtin_nontemporal_load((const nt4*)&a.g0[j]);
+            g1[k] = __builtin_nontemporal_load((const nt4*)&a.g1[j]);
+            if (a.normal_id) on[k] = __builtin_nontemporal_load((const nt4*)&a.normal_id[i]);
+            if (a.albedo_weight) oa[k] = __builtin_nontemporal_load((const nt4*)&a.albedo_weight[i]);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int y = r0 + 4 * k;
+        if (y >= a.height) break;
+        const long long i = (long long)y * a.width + x;
+        auto fold = [&](float old, float s) { return (reset ? 0.0f : f * old) + f * s; };
+        if (a.normal_id) {
+            const nt4 o = { fold(on[k].x, g0[k].x), fold(on[k].y, g0[k].y), fold(on[k].z, g0[k].z), g0[k].w };
+            __builtin_nontemporal_store(o, (nt4*)&a.normal_id[i]);
+        }
+        if (a.albedo_weight) {
+            const nt4 o = { fold(oa[k].x, g1[k].x), fold(oa[k].y, g1[k].y), fold(oa[k].z, g1[k].z), fold(oa[k].w, 1.0f) };
+            __builtin_nontemporal_store(o, (nt4*)&a.albedo_weight[i]);
+        }
+    }
+}
+// On the main stream right after the draw's pt_blend (or the queued backends' finish pass, from their per-pixel
+// G-buffer), so folds keep the draws' order while their path tracing overlaps: one-wave workgroups that stride
+// over (64 columns x 4 rows of a band) units, as pt_blend_w. (Fused into pt_blend_w as one launch it measured
+// the same: DESIGN.md §6.) The targets are streamed too: nothing reads them before the next draw's fold.
+__global__ __launch_bounds__(64) void pt_feature_fold(FoldArgs a, int units_x, int units)
+{
+    for (int u = blockIdx.x; u < units; u += gridDim.x) {
+        const int cx = u % units_x, rest = u / units_x;
+        const int band = (rest >> 2) * a.num_parts + a.part;
+        const int x = cx * 64 + threadIdx.x;
+        if (x < a.width) foldRows(a, x, band * kTile + (rest & 3));
     }
 }
 
@@ -704,6 +759,10 @@ PT_WALK_LAUNCHERS(ref)
 PT_WALK_LAUNCHERS(pairs)
 PT_WALK_LAUNCHERS(trail)
 #undef PT_WALK_LAUNCHERS
+// the FEAT variants (pt_trace_feat_<walk>.hip)
+hipError_t pt_launch_trace_feat_ref(int prog, const pt::TraceArgs* a, dim3 grid, dim3 block, hipStream_t s);
+hipError_t pt_launch_trace_feat_pairs(int prog, const pt::TraceArgs* a, dim3 grid, dim3 block, hipStream_t s);
+hipError_t pt_launch_trace_feat_trail(int prog, const pt::TraceArgs* a, dim3 grid, dim3 block, hipStream_t s);
 
 extern "C" {
 
@@ -714,6 +773,14 @@ hipError_t pt_launch_trace(int prog, int count, const pt::TraceArgs* a, int grid
     const dim3 grid(grid_x * pt::kTraceSub, grid_y), block(pt::kTraceBlock);
     // texture-free models (the bench's StanfordBunny) take the variant without PBR code
     prog = pt::resolveProgram(prog, a->uses_albedo || a->uses_bump, a->bvh_walk);
+    if (!count && a->feat0) {   // a timed draw with feature targets bound: the variants that stage the G-buffer
+        switch (prog / pt::PROG_PAIRS) {
+        case pt::WALK_REF: return pt_launch_trace_feat_ref(prog, a, grid, block, s);
+        case pt::WALK_PAIRS: return pt_launch_trace_feat_pairs(prog, a, grid, block, s);
+        case pt::WALK_TRAIL: return pt_launch_trace_feat_trail(prog, a, grid, block, s);
+        default: return hipErrorInvalidValue;
+        }
+    }
     switch (prog / pt::PROG_PAIRS) {
     case pt::WALK_REF: return pt_launch_trace_ref(prog, count, a, grid, block, s);
     case pt::WALK_PAIRS: return pt_launch_trace_pairs(prog, count, a, grid, block, s);
@@ -808,6 +875,15 @@ hipError_t pt_launch_blend(const pt::BlendArgs* a, int bands, hipStream_t s, int
         return hipGetLastError();
     }
     hipLaunchKernelGGL(pt::pt_blend, dim3((a->width + 63) / 64, bands), dim3(256), 0, s, *a);
+    return hipGetLastError();
+}
+
+// the feature fold of a draw over `bands` owned bands: at most `waves` one-wave workgroups (0: one per unit)
+hipError_t pt_launch_feature_fold(const pt::FoldArgs* a, int bands, hipStream_t s, int waves)
+{
+    if (bands <= 0 || a->width <= 0) return hipSuccess;
+    const int ux = (a->width + 63) / 64, units = ux * bands * 4;
+    hipLaunchKernelGGL(pt::pt_feature_fold, dim3(waves > 0 && waves < units ? waves : units), dim3(64), 0, s, *a, ux, units);
     return hipGetLastError();
 }
 

@@ -330,6 +330,17 @@ PT_D void radianceOut(const TraceArgs& a, long long pi, f3 r, float sharp, bool 
     __builtin_nontemporal_store(o, (nt4*)&a.rad[pi]);
 }
 
+// feature buffers: pixel `pi`'s final G-buffer staged for pt_feature_fold (final also when the path goes on
+// into pt_cont: normal, colour and id are written at bounces 0 and 1 only). Streamed like the radiance.
+PT_D void featureOut(const TraceArgs& a, long long pi, const GOut& g)
+{
+    typedef float nt4 __attribute__((ext_vector_type(4)));
+    const nt4 n = { g.nrm.x, g.nrm.y, g.nrm.z, g.id };
+    const nt4 c = { g.col.x, g.col.y, g.col.z, 0.0f };
+    __builtin_nontemporal_store(n, (nt4*)&a.feat0[pi]);
+    __builtin_nontemporal_store(c, (nt4*)&a.feat1[pi]);
+}
+
 PT_D float xorq(float v, int m) { return __shfl_xor(v, m, 64); }
 
 // longest-first dispatch: wave durations (shader clock) in 8 log-scale buckets per octave (pt_order_build)
@@ -401,10 +412,13 @@ PT_D bool tracePlace(const TraceArgs& a, int lane, TracePlace& pl)
     return true;
 }
 
-template <int PROG, bool COUNT, bool CONT>
+// FEAT: the variant of a draw with feature targets bound (pt_trace_feat_<walk>.hip): it also stages the pixel's
+// G-buffer (featureOut). The counting kernels, on no timed path, test the pointer at run time instead.
+template <int PROG, bool COUNT, bool CONT, bool FEAT = false>
 __global__ __launch_bounds__(kTraceBlock, kMinWaves<PROG>) void pt_trace(TraceArgs a)
 {
     static_assert(!CONT || (kHasMesh<PROG> && !COUNT), "late-bounce compaction: mesh programs, timed kernels");
+    static_assert(!FEAT || !COUNT, "feature staging: a variant of the timed kernels");
     // one LDS array: the stack levels (+ the scratch level, kScratchOf) or the trail walk's ring, then
     // the G-buffer's LDS fields (none in some variants: no zero-length array)
     __shared__ float2 lds_stack[kWalkSlotsOf<PROG> * kTraceBlock + (kGoutLdsOf<PROG> * kTraceBlock + 1) / 2];
@@ -515,6 +529,7 @@ __global__ __launch_bounds__(kTraceBlock, kMinWaves<PROG>) void pt_trace(TraceAr
     if (!active || px >= a.width || py >= a.height) return;   // quad helper outside the target, idle lane
     const bool edge = colorDiff >= 1.0f || normalDiff >= 1.0f || objectDiff >= 1.0f;
     const long long pi = (long long)py * a.width + px;
+    if (FEAT || (COUNT && a.feat0)) featureOut(a, pi, g);
     if (CONT && slot >= 0) {   // the path continues in pt_cont, which writes the pixel's radiance
         a.cont_aux[slot] = (unsigned)pi | (edge ? 0x80000000u : 0u);
         return;

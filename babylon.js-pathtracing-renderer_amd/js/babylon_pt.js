@@ -19,6 +19,7 @@
 //   new BABYLON.EffectWrapper({...})              -> pt_effect_create (GLSL text -> program) (:773-811)
 //   effect.setFloat/.../setMatrix/setTexture      -> pt_set_float / pt_set_int / pt_set_texture (:813-848)
 //   new BABYLON.EffectRenderer(engine).render()   -> pt_render (:1230-1235)
+//   effect.setFeatureTargets(normalRT, albedoRT)  -> pt_set_feature_targets (extension: accumulated G-buffer)
 'use strict';
 const fs = require('fs');
 const path = require('path');
@@ -318,6 +319,17 @@ function install(BABYLON, opts) {
       if (t && !t._pt && t._ptForeign === undefined) adoptForeign(this._ctx, t);
       const h = t ? (t._pt || t._ptForeign || null) : null;
       if (this._pt) check(this._ctx, addon.pt_set_texture(this._pt, n, h), 'setTexture ' + n);
+      return this;
+    }
+    // MI355X extension (pt_set_feature_targets): while RenderTargetTextures are bound here, every draw of
+    // this path-tracing effect also accumulates its G-buffer into them in place, by the beauty's history
+    // rule: normalRT = (sum of objectNormal, this draw's objectID), albedoRT = (sum of objectColor, weight).
+    // null / undefined: that buffer is not produced; both: the feature is off
+    setFeatureTargets(normalRT, albedoRT) {
+      if (this._pt) {
+        check(this._ctx, addon.pt_set_feature_targets(this._pt, normalRT ? normalRT._pt : null, albedoRT ? albedoRT._pt : null),
+          'setFeatureTargets');
+      }
       return this;
     }
   }

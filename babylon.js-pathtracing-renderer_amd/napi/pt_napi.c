@@ -373,6 +373,13 @@ static napi_value ContStats(napi_env env, napi_callback_info info)
     for (uint32_t i = 0; i < 2; i++) napi_set_element(env, r, i, num(env, (double)s[i]));
     return r;
 }
+/* pt_set_feature_targets(effect, normalId | null, albedoWeight | null) -> status */
+static napi_value SetFeatureTargets(napi_env env, napi_callback_info info)
+{
+    napi_value a[MAXARGS]; if (args(env, info, a, 1) < 0) return NULL;
+    return num(env, pt_set_feature_targets((pt_effect*)handle(env, a[0]), (pt_texture*)handle(env, a[1]),
+                                           (pt_texture*)handle(env, a[2])));
+}
 /* pt_bvh_build(aabbIn: Float32Array (9 per triangle), work: Uint32Array, out: Float32Array) -> node count */
 static napi_value BvhBuild(napi_env env, napi_callback_info info)
 {
@@ -449,6 +456,7 @@ static napi_value Init(napi_env env, napi_value exports)
         { "pt_last_render_ms", LastRenderMs }, { "pt_timing_begin", TimingBegin }, { "pt_timing_end", TimingEnd },
         { "pt_timing_latency", TimingLatency },
         { "pt_set_counting", SetCounting }, { "pt_read_counters", ReadCounters }, { "pt_reset_counters", ResetCounters }, { "pt_queue_stats", QueueStats }, { "pt_cont_stats", ContStats },
+        { "pt_set_feature_targets", SetFeatureTargets },
         { "pt_bvh_build", BvhBuild }, { "pt_bvh_build_gpu", BvhBuildGpu },
         { "pt_jpeg_size", JpegSize }, { "pt_jpeg_decode_rgba8", JpegDecode }, { "pt_version", Version },
     };

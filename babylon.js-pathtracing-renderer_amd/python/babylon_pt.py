@@ -40,7 +40,7 @@ SYMBOLS = [
     "pt_render_target_resize", "pt_texture_size", "pt_texture_destroy",
     "pt_render", "pt_read_pixels", "pt_write_pixels",
     "pt_set_row_partition", "pt_set_output_partition", "pt_canvas_wrap", "pt_set_backend", "pt_set_bvh_layout", "pt_bvh_layout_used", "pt_set_stream", "pt_texture_device_ptr", "pt_last_render_ms", "pt_timing_begin", "pt_timing_end", "pt_timing_latency",
-    "pt_set_counting", "pt_read_counters", "pt_reset_counters", "pt_queue_stats", "pt_cont_stats", "pt_math_probe", "pt_math_exhaustive", "pt_bvh_build", "pt_bvh_build_gpu", "pt_jpeg_size", "pt_jpeg_decode_rgba8", "pt_version",
+    "pt_set_counting", "pt_read_counters", "pt_reset_counters", "pt_queue_stats", "pt_cont_stats", "pt_set_feature_targets", "pt_math_probe", "pt_math_exhaustive", "pt_bvh_build", "pt_bvh_build_gpu", "pt_jpeg_size", "pt_jpeg_decode_rgba8", "pt_version",
 ]
 
 _lib = None
@@ -90,6 +90,7 @@ def lib():
         "pt_math_probe": ([vp, i32, vp, vp, vp, i32], i32),
         "pt_math_exhaustive": ([vp, i32, vp], i32),
         "pt_cont_stats": ([vp, ctypes.POINTER(ctypes.c_uint64)], i32),
+        "pt_set_feature_targets": ([vp, vp, vp], i32),
         "pt_queue_stats": ([vp, ctypes.POINTER(ctypes.c_uint32)], i32), "pt_version": ([], ctypes.c_char_p),
     }
     for name, (args, res) in sig.items():
@@ -408,6 +409,16 @@ class Effect:
             return
         self.engine.check(lib().pt_set_texture(self.handle, name.encode(), h), "setTexture")
         self._tex[name] = (tex, h)
+
+    def setFeatureTargets(self, normal_id=None, albedo_weight=None):
+        """MI355X extension (pt_set_feature_targets): while render targets are bound here, every draw of this
+        path-tracing effect also accumulates its G-buffer into them in place, by the beauty's history rule -
+        normal_id = (sum of objectNormal, this draw's objectID), albedo_weight = (sum of objectColor, weight);
+        xyz / albedo_weight.w is the mean over the samples the beauty holds. None: that buffer is not
+        produced; both None turns the feature off."""
+        self.engine.check(lib().pt_set_feature_targets(self.handle, normal_id.handle if normal_id is not None else None,
+                                                       albedo_weight.handle if albedo_weight is not None else None),
+                          "setFeatureTargets")
 
 
 class EffectWrapper:

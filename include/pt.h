@@ -237,6 +237,24 @@ int pt_queue_stats(pt_ctx* ctx, uint32_t out[16]);
  * it (not mod 2^16 as in pt_queue_stats); with several parts, summed over them. Each draw's history
  * blend adds its record count to the total as it zeroes it, so the path-tracing kernels pay nothing. */
 int pt_cont_stats(pt_ctx* ctx, uint64_t out[2]);
+/* Feature buffers: bind (or with NULLs unbind) feature targets to a path-tracing effect. Both are RGBA32F
+ * render targets of the draw target's size; either may be NULL (that buffer is then not produced), both NULL
+ * turns the feature off. While targets are bound, every pt_render of the effect also folds this draw's
+ * G-buffer sample - CalculateRadiance's objectNormal / objectColor / objectID, the values the 2x2 edge test
+ * reads - into them in place, on the owned 16-row bands, by the beauty's own history rule
+ * (js/PathTracingCommon.js:1326-1337). With F = uFrameCounter, M = uCameraIsMoving,
+ *   h = F == 1 ? 0 : (M ? 0.5 : 1)     (at F == 1 the history term is +0.0, still added)
+ *   s = (F != 1 && M) ? 0.5 : 1
+ *   normal_id.xyz     = h * old.xyz + s * objectNormal     normal_id.w     = objectID of this draw
+ *   albedo_weight.xyz = h * old.xyz + s * objectColor      albedo_weight.w = h * old.w + s
+ * so xyz / albedo_weight.w is the mean over the samples the beauty currently holds. The beauty target, the
+ * canvas and every counter are bit for bit what they are without features. The fold runs on the context's
+ * stream after the draw's own accumulation: a sync or a read comes after the folds of all earlier draws.
+ * PT_ERR_ARG for a screenCopy / screenOutput effect or a texture that is not a render target of this
+ * context; pt_render returns PT_ERR_STATE when a bound target's size differs from the draw target's, or
+ * when it is the draw target, the bound previousBuffer or the other feature target. Destroying a bound
+ * texture unbinds it. */
+int pt_set_feature_targets(pt_effect* fx, pt_texture* normal_id, pt_texture* albedo_weight);
 /* Device self-test of the pinned GLSL built-ins (ops as the oracle's pto_math_probe). */
 int pt_math_probe(pt_ctx* ctx, int op, const float* x, const float* y, float* out, int n);
 /* Exhaustive device self-test of a fast built-in sequence against the IEEE operation it replaces,

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-kernel VGPR / scratch / occupancy of a HIP source (clang's kernel-resource-usage remarks)."""
+"""Per-kernel VGPR / SGPR / scratch / occupancy / LDS of a HIP source (clang's kernel-resource-usage remarks)."""
 import re
 import subprocess
 import sys
@@ -17,10 +17,10 @@ for line in out.splitlines():
         cur = {"name": m.group(1)}
         rows.append(cur)
         continue
-    for key in ("VGPRs", "AGPRs", "ScratchSize \\[bytes/lane\\]", "Occupancy \\[waves/SIMD\\]", "LDS Size \\[bytes/block\\]"):
+    for key in ("VGPRs", "AGPRs", "SGPRs", "ScratchSize \\[bytes/lane\\]", "Occupancy \\[waves/SIMD\\]", "LDS Size \\[bytes/block\\]"):
         m = re.search(key + r": (\d+)", line)
         if m and cur is not None:
             cur[key.split()[0]] = int(m.group(1))
 for r in rows:
-    print("%-70s vgpr %3s scratch %4s occ %s lds %s" % (r["name"][:70], r.get("VGPRs"), r.get("ScratchSize"),
-                                                       r.get("Occupancy"), r.get("LDS")))
+    print("%-70s vgpr %3s sgpr %3s scratch %4s occ %s lds %s" % (r["name"][:70], r.get("VGPRs"), r.get("SGPRs"),
+                                                                r.get("ScratchSize"), r.get("Occupancy"), r.get("LDS")))

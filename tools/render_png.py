@@ -3,7 +3,11 @@
 (screenOutput: 5x5 denoise, 1/N, Reinhard, gamma) as a PNG - a visual check of the converged image
 (BASELINE configs[4]-style: many samples + the output filter). Prints Mpaths/s over the run.
 
-usage: render_png.py [--workload dragon|bunny|helmet] [--size WxH] [--frames K] --out PATH"""
+With --features DIR the accumulated G-buffer (Effect.setFeatureTargets) is saved beside it: normal.png
+(xyz / weight * 0.5 + 0.5), albedo.png (xyz / weight) and id.png (the last frame's object id, modulo a small
+palette).
+
+usage: render_png.py [--workload dragon|bunny|helmet] [--size WxH] [--frames K] [--features DIR] --out PATH"""
 import argparse
 import os
 import sys
@@ -23,6 +27,7 @@ ap.add_argument("--workload", choices=("dragon", "bunny", "helmet"), default="dr
 ap.add_argument("--size", default="1920x1080")
 ap.add_argument("--frames", type=int, default=256)
 ap.add_argument("--out", required=True)
+ap.add_argument("--features", metavar="DIR", help="also save normal.png, albedo.png and id.png there")
 a = ap.parse_args()
 W, Hh = (int(v) for v in a.size.lower().split("x"))
 meta = H.stream("hdri_helmet_320x180" if a.workload == "helmet" else "gltf_bunny_1080p")
@@ -34,6 +39,10 @@ if a.workload == "helmet":
     for kind, sampler in H.PBR_SAMPLERS.items():
         p.textures[sampler] = bp.Texture(e, maps[kind], name=kind)
 e.resize_canvas(W, Hh)
+feat = None
+if a.features:
+    feat = (bp.RenderTargetTexture("featureNormalId", (W, Hh), e), bp.RenderTargetTexture("featureAlbedoWeight", (W, Hh), e))
+    p.wrappers[H.path_call(p.meta["frames"][0])["effect"]].effect.setFeatureTargets(*feat)
 for call in p.meta["frames"][0]:
     p.play_call(call)
 e.sync()
@@ -46,5 +55,20 @@ dt = time.perf_counter() - t0
 img = e.read_canvas(W, Hh)[::-1, :, :3]          # GL rows bottom-up -> image rows top-down
 from PIL import Image                             # noqa: E402
 Image.fromarray(np.ascontiguousarray(img)).save(a.out)
+if feat:
+    PALETTE = np.array([[0, 0, 0], [230, 25, 75], [60, 180, 75], [255, 225, 25], [0, 130, 200], [245, 130, 48],
+                        [145, 30, 180], [70, 240, 240], [240, 50, 230], [210, 245, 60], [250, 190, 212], [0, 128, 128]], np.uint8)
+    nid, alb = (t.read()[::-1] for t in feat)
+    wgt = np.maximum(alb[..., 3:4], np.float32(1e-20))   # (the weight is one value for the whole frame, > 0)
+
+    def u8(x):
+        return np.ascontiguousarray(np.clip(np.rint(x * 255.0), 0, 255).astype(np.uint8))
+
+    os.makedirs(a.features, exist_ok=True)
+    Image.fromarray(u8(nid[..., :3] / wgt * 0.5 + 0.5)).save(os.path.join(a.features, "normal.png"))
+    Image.fromarray(u8(alb[..., :3] / wgt)).save(os.path.join(a.features, "albedo.png"))
+    Image.fromarray(np.ascontiguousarray(PALETTE[nid[..., 3].astype(np.int64) % len(PALETTE)])).save(os.path.join(a.features, "id.png"))
+    print("features: weight %.1f, %d object ids, saved normal.png albedo.png id.png in %s" % (
+        float(alb[0, 0, 3]), len(np.unique(nid[..., 3])), a.features))
 print("%s %dx%d %d frames: %.1f Mpaths/s, mean %.1f, saved %s" % (a.workload, W, Hh, a.frames,
       W * Hh * a.frames / dt / 1e6, img.mean(), a.out))
