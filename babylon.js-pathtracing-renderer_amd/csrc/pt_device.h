@@ -92,6 +92,18 @@ template <int P> constexpr bool kScratchOf = !kPairs8<P>;
 // LDS float2 slots per lane a walk of program P needs: stack levels (+ the scratch level), or the ring
 template <int P> constexpr int kWalkSlotsOf = kTrail<P> ? kRingOf<P> : kStackLdsOf<P> + (kScratchOf<P> ? 1 : 0);
 
+// Per-lane indices that are a wave-uniform base plus the lane id (the slab index of a lane of the grid, a
+// pixel of the wave's tile) cross the BVH walk as the base, in an SGPR, in the 8-wave variants: the users
+// add the lane id where they need the index. laneNow() forms it there (v_mbcnt, as volatile asm: neither
+// hoisted out of the bounce loop nor merged with another use, so no VGPR holds it across the walk).
+template <int P> constexpr bool kWaveBaseOf = kPairs8<P>;
+PT_D unsigned laneNow()
+{
+    unsigned l;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+    return l;
+}
+
 typedef float vf2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) vf2 lds_float2;
 typedef __attribute__((address_space(1))) vf2 glb_float2;

@@ -77,7 +77,8 @@ typedef __attribute__((address_space(1))) float glb_float;
 // hit's colour, and every object's hit colour is a constant of the object (objectMaterial), so the
 // end of the path recomputes it from the bounce-0 id - unless bounce 1 after METAL replaced the id,
 // when pinCol stores it first (bit 31 then says so).
-template <int LS, int NF = 6>
+// BASE (the 8-wave variants): `gi` is the wave's base, the lane id is added at the use (pt_device.h laneNow)
+template <int LS, int NF = 6, bool BASE = false>
 struct GOutLds {
     static constexpr bool kColById = NF <= 3;
     lds_float* p;
@@ -89,7 +90,7 @@ struct GOutLds {
     // bounce loop as six 64-bit pointers)
     PT_D unsigned at(int f) const
     {
-        unsigned i = gi;
+        unsigned i = BASE ? gi + laneNow() : gi;
         asm volatile("" : "+v"(i));
         return i + (unsigned)(f - NF) * gs;
     }

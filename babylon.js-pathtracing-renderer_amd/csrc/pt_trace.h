@@ -9,6 +9,7 @@
 #include "pt_args.h"
 #include "pt_device.h"
 #include "pt_glsl.h"
+#include "pt_pathstate.h"
 #include "pt_program.h"
 #ifdef PT_SECPROF
 #define PT_SECPROF_ON 1
@@ -21,13 +22,15 @@ using namespace ptg;
 namespace pt {
 
 // LS = lanes of the block = the stride of one stack level in LDS; NL = stack levels in LDS
-template <int LS, int NL, bool SCRATCH>
+// BASE (the 8-wave variants): `deep` is the wave's base, the lane id is added at the use (pt_device.h laneNow)
+template <int LS, int NL, bool SCRATCH, bool BASE>
 struct MegaStack {
     lds_float2* lds;
     unsigned slot;
     glb_float2* slab;     // the spill slab (wave-uniform base) ...
     unsigned deep;        // ... and this lane's index in it: level NL, levels `stride` apart
     unsigned stride;      //     (32-bit: a 64-bit per-lane pointer costs two VGPRs for the whole path)
+    PT_D unsigned at() const { return BASE ? deep + laneNow() : deep; }
 #ifdef PT_SECPROF
     mutable unsigned n_get = 0, n_get_slab = 0, n_put = 0, n_put_slab = 0;
 #define PT_SLABCOUNT(x) x
@@ -42,7 +45,7 @@ struct MegaStack {
         vf2 e = lds[(unsigned)min(si, NL - 1) * LS + slot];
         if (si >= NL) {
             const vf2 s = { sentinel.x, sentinel.y };
-            e = si < kStackLevels ? slab[(unsigned)(si - NL) * stride + deep] : s;
+            e = si < kStackLevels ? slab[(unsigned)(si - NL) * stride + at()] : s;
         }
         return make_float2(e.x, e.y);
     }
@@ -61,7 +64,7 @@ struct MegaStack {
         else if (si < NL) lds[(unsigned)si * LS + slot] = v;
         if (si >= NL) {
             if (si >= kStackLevels) return false;
-            slab[(unsigned)(si - NL) * stride + deep] = v;
+            slab[(unsigned)(si - NL) * stride + at()] = v;
         }
         return true;
     }
@@ -97,10 +100,30 @@ PT_D void meshHit(const TraceArgs& a, float triID, float triU, float triV, Hit& 
     h.id = meshObjectId<PROG>(a);
 }
 
+// The analytic winner's object-space normal formed after the walk (the 8-wave mesh programs with the two
+// spheres): unitSphere's own expression over the same transformed ray and the same t - the walk leaves h.t as
+// it was when the mesh does not win - so the same bits, and three registers fewer across the walk.
+template <int PROG> constexpr bool kNormalAfter = kHasMesh<PROG> && !kIsQuadric<PROG>;
+PT_D f3 sphereNormal(const TraceArgs& a, f3 rayO, f3 rayD, const Hit& h)
+{
+    f3 n = mk(0, 0, 0);
+#pragma unroll 1
+    for (int s = 0; s < 2; s++) {   // (rolled, as analyticNearest's: the sphere is read through the scalar cache)
+        if (h.id != s) continue;
+        const SphereArg& S = a.sph[s];
+        const f3 ro = mul(S.inv, rayO, 1.0f), rd = mul(S.inv, rayD, 0.0f);
+        const f3 x = ro + rd * h.t;
+        n = mk(2.0f * x.x, 2.0f * x.y, 2.0f * x.z);
+    }
+    return n;
+}
+
 // SceneIntersect: js/BabylonPathTracing_FragmentShader.js:47-112 (Cornell),
 // js/TransformedQuadricGeometry_FragmentShader.js:77-317 (quadrics) and
 // js/GLTFModelPathTracing_FragmentShader.js:116-346 (glTF, with the BVH walk)
-template <int PROG, bool COUNT, int LS>
+// SLIM (pt_trace and pt_cont of the 8-wave variants, kWaveBaseOf): fewer values live across the walk - `deep` is the
+// wave's base (MegaStack BASE), the sphere normal is formed after the walk (kNormalAfter)
+template <int PROG, bool COUNT, int LS, bool SLIM>
 PT_D void sceneIntersect(const TraceArgs& a, f3 rayO, f3 rayD, Hit& h, float2* lds, unsigned lane_slot,
                          unsigned deep, Cnt& cnt, bool firstHit)
 {
@@ -126,7 +149,7 @@ PT_D void sceneIntersect(const TraceArgs& a, f3 rayO, f3 rayD, Hit& h, float2* l
     f3 inv = mk(grcp(D.x), grcp(D.y), grcp(D.z));
     const bool dbl = (!a.uses_albedo && a.model_mat == TRANSPARENT);
     BvhResult br = { 0.0f, 0.0f, 0.0f, false, 1u, 0u, 0u };
-    MegaStack<LS, kStackLdsOf<PROG>, kScratchOf<PROG>> st{ (lds_float2*)lds, lane_slot, (glb_float2*)a.spill, deep, a.spill_stride };
+    MegaStack<LS, kStackLdsOf<PROG>, kScratchOf<PROG>, SLIM> st{ (lds_float2*)lds, lane_slot, (glb_float2*)a.spill, deep, a.spill_stride };
     if (kPairs<PROG>) {   // the root's box from the kernel arguments (the same floats as texels 0-1)
         const float* rb = a.bvh_root_box;
         const float rootT = box(mk(rb[0], rb[1], rb[2]), mk(rb[3], rb[4], rb[5]), O, inv);
@@ -162,12 +185,28 @@ PT_D void sceneIntersect(const TraceArgs& a, f3 rayO, f3 rayD, Hit& h, float2* l
         h.color = mk(1.0f, 1.0f, 1.0f);
         h.id = meshObjectId<PROG>(a);
     } else if (br.lookup) meshHit<PROG, COUNT>(a, br.triID, br.triU, br.triV, h, cnt);
-    else analyticAttributes<PROG>(a, h, sn);
+    else {
+        if (SLIM && kNormalAfter<PROG>) sn = sphereNormal(a, rayO, rayD, h);
+        analyticAttributes<PROG>(a, h, sn);
+    }
     PT_SEC(cnt, 3);
 }
 
+// PState's small integers and flags to and from their one-word form (pt_pathstate.h)
+PT_D unsigned pathBitsOf(const PState& s)
+{
+    return pathBitsPack(s.diffuseCount, s.hitType, s.bounce, s.coat, s.specular, s.sampleLight);
+}
+PT_D void pathBitsTo(PState& s, unsigned bits)
+{
+    const PathBits b = pathBitsUnpack(bits);
+    s.diffuseCount = b.diffuseCount; s.hitType = b.hitType; s.bounce = b.bounce;
+    s.coat = b.coat; s.specular = b.specular; s.sampleLight = b.sampleLight;
+}
+
 // One iteration of CalculateRadiance's loop: SceneIntersect, then the shading step
-template <int PROG, bool COUNT, int LS, class G>
+// SLIM: sceneIntersect's, and the path's small integers and flags cross the walk as one register
+template <int PROG, bool COUNT, int LS, bool SLIM, class G>
 PT_D bool bounceStep(const TraceArgs& a, Path& p, PState& s, G& g, f3& accum, float2* lds, unsigned lane_slot,
                      unsigned deep, Cnt& cnt)
 {
@@ -184,7 +223,13 @@ PT_D bool bounceStep(const TraceArgs& a, Path& p, PState& s, G& g, f3& accum, fl
     // (profiles/r04k_envmx_anyhit.txt, r04q_envmx_anyhit_last.txt)
     const bool lastOk = !kHasTex<PROG> && !a.uses_albedo &&
                         (a.model_mat == DIFFUSE || a.model_mat == METAL || a.model_mat == TRANSPARENT);
-    sceneIntersect<PROG, COUNT, LS>(a, p.ro, p.rd, h, lds, lane_slot, deep, cnt, s.sampleLight || (s.bounce == 5 && lastOk));
+    const bool firstHit = s.sampleLight || (s.bounce == 5 && lastOk);
+    // the path's small integers and flags cross the walk as one register (the record's word, pt_pathstate.h;
+    // the empty asm keeps the compiler from carrying the six fields instead)
+    unsigned bits = pathBitsOf(s);
+    if (SLIM) asm volatile("" : "+v"(bits));
+    sceneIntersect<PROG, COUNT, LS, SLIM>(a, p.ro, p.rd, h, lds, lane_slot, deep, cnt, firstHit);
+    if (SLIM) { asm volatile("" : "+v"(bits)); pathBitsTo(s, bits); }
     return shadeStep<PROG, COUNT, G>(a, p, s, g, accum, h, cnt);
 }
 
@@ -195,27 +240,22 @@ PT_D bool bounceStep(const TraceArgs& a, Path& p, PState& s, G& g, f3& accum, fl
 // The G-buffer's normal, colour and id are final from bounce 2 on (the GLSL writes them at bounces 0 and 1).
 PT_D void contStore(const TraceArgs& a, unsigned slot, const Path& p, const PState& s)
 {
-    const unsigned bits = ((unsigned)s.diffuseCount & 0xffu) | (((unsigned)s.hitType & 0xffu) << 8) |
-                          (((unsigned)s.bounce & 0xffu) << 16) | (s.coat ? 1u << 24 : 0u) |
-                          (s.specular ? 1u << 25 : 0u) | (s.sampleLight ? 1u << 26 : 0u);
+    const unsigned bits = pathBitsOf(s);
     float4* r = a.cont_rec + 4ull * slot;
     r[0] = make_float4(p.ro.x, p.ro.y, p.ro.z, p.rd.x);
     r[1] = make_float4(p.rd.y, p.rd.z, s.mask.x, s.mask.y);
     r[2] = make_float4(s.mask.z, s.roughness, __uint_as_float(p.s0), __uint_as_float(p.s1));
     r[3] = make_float4(__uint_as_float(p.bn), __uint_as_float(bits), 0.0f, 0.0f);
 }
-PT_D void contLoad(const TraceArgs& a, unsigned slot, Path& p, PState& s)
+// (the small integers and flags stay the record's word, `bits`: pt_cont carries them so between its bounces)
+PT_D void contLoad(const TraceArgs& a, unsigned slot, Path& p, f3& mask, float& roughness, unsigned& bits)
 {
     const float4* r = a.cont_rec + 4ull * slot;
     const float4 r0 = r[0], r1 = r[1], r2 = r[2], r3 = r[3];
     p.ro = mk(r0.x, r0.y, r0.z); p.rd = mk(r0.w, r1.x, r1.y);
-    s.mask = mk(r1.z, r1.w, r2.x); s.roughness = r2.y;
+    mask = mk(r1.z, r1.w, r2.x); roughness = r2.y;
     p.s0 = __float_as_uint(r2.z); p.s1 = __float_as_uint(r2.w); p.bn = __float_as_uint(r3.x);
-    const unsigned bits = __float_as_uint(r3.y);
-    s.diffuseCount = (int)(bits & 0xffu);
-    s.hitType = (int)(signed char)((bits >> 8) & 0xffu);
-    s.bounce = (int)((bits >> 16) & 0xffu);
-    s.coat = (bits >> 24) & 1u; s.specular = (bits >> 25) & 1u; s.sampleLight = (bits >> 26) & 1u;
+    bits = __float_as_uint(r3.y);
 }
 // the G-buffer of a continued path: only the sharpness can still change, in the same bits of Path::bn
 // as pt_trace keeps it (GOutLds)
@@ -288,16 +328,18 @@ PT_D void contRank(const TraceArgs& a, int slot, const Path& p, const PState& s,
 // over the ballot of the storing lanes.
 // CONT is a kernel variant of its own (pt_trace<PROG, false, true>): the check in the bounce loop costs the
 // 8-wave variants at their 64-VGPR budget even where it never fires (dragon stand-in +14 %, r05g)
-template <int PROG, bool COUNT, int LS, bool CONT, class G>
+// `insideNow()`: whether the lane's pixel lies inside the target (asked only where a wave stores its paths)
+template <int PROG, bool COUNT, int LS, bool CONT, class G, class IN>
 PT_D f3 radiance(const TraceArgs& a, Path& p, G& g, float2* lds, unsigned lane_slot, unsigned deep, Cnt& cnt,
-                 bool inside, int& slot)
+                 IN insideNow, int& slot)
 {
     PState s;
     pathBegin(s, g);
     f3 accum = mk(0, 0, 0);
 #pragma unroll 1
-    while (bounceStep<PROG, COUNT, LS, G>(a, p, s, g, accum, lds, lane_slot, deep, cnt)) {
+    while (bounceStep<PROG, COUNT, LS, kWaveBaseOf<PROG>, G>(a, p, s, g, accum, lds, lane_slot, deep, cnt)) {
         if (CONT && (unsigned)s.bounce >= a.cont_bounce && (unsigned)__popcll(__ballot(1)) <= a.cont_lanes) {
+            const bool inside = insideNow();
             const unsigned long long st = __ballot(inside);
             const int lead = __ffsll((long long)__ballot(1)) - 1;
             unsigned base = 0;
@@ -341,6 +383,12 @@ PT_D void featureOut(const TraceArgs& a, long long pi, const GOut& g)
     __builtin_nontemporal_store(c, (nt4*)&a.feat1[pi]);
 }
 
+// how many of `mask`'s lanes lie below this one (v_mbcnt: no lane mask of its own held in registers)
+PT_D unsigned lanesBelow(unsigned long long mask)
+{
+    return __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
+}
+
 PT_D float xorq(float v, int m) { return __shfl_xor(v, m, 64); }
 
 // longest-first dispatch: wave durations (shader clock) in 8 log-scale buckets per octave (pt_order_build)
@@ -367,7 +415,17 @@ constexpr int kTraceSub = 4;   // workgroups per 16x16 tile
 struct TracePlace {
     int px, py, part;
     unsigned costIdx;
+    int x0, y0;   // the wave's block (8x8, or a split tile's quadrant): wave-uniform, (px, py) = (x0, y0) + placeLane
 };
+// lane bits (x0, y0, x1, x2, y1, y2) of an 8x8 block, or (x0, y0, x1, y1) of part `part` of a split tile's quadrant
+PT_D void placeLane(int part, int lane, int& lx, int& ly)
+{
+    if (part < 0) { lx = (lane & 1) | ((lane >> 1) & 6); ly = ((lane >> 1) & 1) | ((lane >> 3) & 6); }
+    else {
+        lx = (part & 1) * 4 + ((lane & 1) | ((lane >> 1) & 2));
+        ly = (part >> 1) * 4 + (((lane >> 1) & 1) | ((lane >> 2) & 2));
+    }
+}
 PT_D bool tracePlace(const TraceArgs& a, int lane, TracePlace& pl)
 {
     int wave, part = -1;
@@ -397,16 +455,13 @@ PT_D bool tracePlace(const TraceArgs& a, int lane, TracePlace& pl)
     const unsigned tile = a.order ? a.order[rank] : slot;
     const int tx = (int)(tile % tiles_x);
     const unsigned bY = tile / tiles_x;
-    // lane bits (x0, y0, x1, x2, y1, y2) of an 8x8 block, or (x0, y0, x1, y1) of a split tile's 4x4
     int lx, ly;
-    if (part < 0) { lx = (lane & 1) | ((lane >> 1) & 6); ly = ((lane >> 1) & 1) | ((lane >> 3) & 6); }
-    else {
-        lx = (part & 1) * 4 + ((lane & 1) | ((lane >> 1) & 2));
-        ly = (part >> 1) * 4 + (((lane >> 1) & 1) | ((lane >> 2) & 2));
-    }
+    placeLane(part, lane, lx, ly);
     const int band = (int)bY * a.num_parts + a.part;            // global 16-row band of this block
-    pl.px = tx * kTile + (wave & 1) * 8 + lx;
-    pl.py = band * kTile + (wave >> 1) * 8 + ly;
+    pl.x0 = tx * kTile + (wave & 1) * 8;
+    pl.y0 = band * kTile + (wave >> 1) * 8;
+    pl.px = pl.x0 + lx;
+    pl.py = pl.y0 + ly;
     pl.part = part;
     pl.costIdx = tile * 4u + (unsigned)wave;
     return true;
@@ -424,21 +479,31 @@ __global__ __launch_bounds__(kTraceBlock, kMinWaves<PROG>) void pt_trace(TraceAr
     __shared__ float2 lds_stack[kWalkSlotsOf<PROG> * kTraceBlock + (kGoutLdsOf<PROG> * kTraceBlock + 1) / 2];
     float* const lds_gout = (float*)(lds_stack + kWalkSlotsOf<PROG> * kTraceBlock);
     const unsigned tid = threadIdx.x;
-    const int lane = tid & 63;
+    int lane = tid & 63;
     const unsigned long long t_start = clock64();
 #ifdef PT_SECPROF
     const unsigned long long w0_ = wall_clock64();
 #endif
     TracePlace pl;
     if (!tracePlace(a, lane, pl)) return;   // the grid's padding
-    const int px = pl.px, py = pl.py;
+    int px = pl.px, py = pl.py;
+    // the 8-wave variants (kWaveBaseOf): what places the wave is wave-uniform and stays in SGPRs; the lane's pixel
+    // and slab index are formed from it and the lane id where they are used, not carried across the walks
+    constexpr bool kWaveBase = kWaveBaseOf<PROG>;
+    if (kWaveBase) {
+        pl.x0 = __builtin_amdgcn_readfirstlane(pl.x0); pl.y0 = __builtin_amdgcn_readfirstlane(pl.y0);
+        pl.part = __builtin_amdgcn_readfirstlane(pl.part); pl.costIdx = __builtin_amdgcn_readfirstlane(pl.costIdx);
+    }
     // stack levels >= kStackLds: a global slab [level][lane of the grid] (a private array would be
     // scratch, which the runtime reserves for every resident wave)
-    const unsigned deep = (blockIdx.y * gridDim.x + blockIdx.x) * kTraceBlock + tid;
+    const unsigned deep = (blockIdx.y * gridDim.x + blockIdx.x) * kTraceBlock + (kWaveBase ? 0u : tid);
 
     // lanes whose whole 2x2 quad lies beyond the (even-rounded) target do no work; quad helpers
     // that only complete a quad at an odd edge are shaded like GL helper invocations
-    const bool active = px < ((a.width + 1) & ~1) && py < ((a.height + 1) & ~1) && (pl.part < 0 || lane < (int)(64u / kSplitParts));
+    auto activeAt = [&](int x, int y, int ln) {
+        return x < ((a.width + 1) & ~1) && y < ((a.height + 1) & ~1) && (pl.part < 0 || ln < (int)(64u / kSplitParts));
+    };
+    bool active = activeAt(px, py, lane);
     Cnt cnt = { 0, 0, 0, 0, 0, 0, 0 };
 #ifdef PT_SECPROF
     __shared__ unsigned long long lds_sec[16];
@@ -455,14 +520,28 @@ __global__ __launch_bounds__(kTraceBlock, kMinWaves<PROG>) void pt_trace(TraceAr
         : nullptr;
     Path p;
     p.bn = 0u;
-    GOutLds<kTraceBlock, kGoutLdsOf<PROG>> gl{ (lds_float*)lds_gout, tid, gx, deep, a.spill_stride, &p.bn };
+    GOutLds<kTraceBlock, kGoutLdsOf<PROG>, kWaveBase> gl{ (lds_float*)lds_gout, tid, gx, deep, a.spill_stride, &p.bn };
     gl.clear();   // pinned: the `out` parameters of CalculateRadiance start at 0 (also lanes without a path)
     f3 r = mk(0, 0, 0);
     int slot = -1;   // late-bounce compaction: this lane's path record for pt_cont
     if (active) {
         cameraRay(a, px, py, p);
         PT_SEC(cnt, 0);
-        r = radiance<PROG, COUNT, kTraceBlock, CONT>(a, p, gl, lds_stack, tid, deep, cnt, px < a.width && py < a.height, slot);
+        const bool inside0 = px < a.width && py < a.height;
+        auto insideNow = [&]() {
+            if (!kWaveBase) return inside0;
+            int lx, ly;
+            placeLane(pl.part, (int)laneNow(), lx, ly);
+            return pl.x0 + lx < a.width && pl.y0 + ly < a.height;
+        };
+        r = radiance<PROG, COUNT, kTraceBlock, CONT>(a, p, gl, lds_stack, tid, deep, cnt, insideNow, slot);
+    }
+    if (kWaveBase) {   // the lane's pixel again, from the wave's block and the lane id
+        lane = (int)laneNow();
+        int lx, ly;
+        placeLane(pl.part, lane, lx, ly);
+        px = pl.x0 + lx; py = pl.y0 + ly;
+        active = activeAt(px, py, lane);
     }
     PT_SEC(cnt, 4);
     const GOut g = gl.load([&](float id) {
@@ -552,14 +631,15 @@ __global__ __launch_bounds__(kTraceBlock, kMinWaves<PROG>) void pt_cont(TraceArg
     const unsigned n = a.cont_count[0];
     unsigned* const head = a.cont_count + 1;   // the queue's next record (zeroed with the counter by pt_blend)
     bool more = true;                          // the queue may still hold records
-    const unsigned deep = blockIdx.x * kTraceBlock + lane;
-    const unsigned long long below = (1ull << lane) - 1ull;
+    const unsigned deep = blockIdx.x * kTraceBlock + (kWaveBaseOf<PROG> ? 0u : lane);   // (kWaveBaseOf: the wave's base)
     Cnt cnt = { 0, 0, 0, 0, 0, 0, 0 };
     Path p;
     p.bn = 0u;
-    PState s;
+    // the path's state between two bounces: the ray and rng (p), the throughput, the roughness, the record's word
+    f3 mask = mk(0, 0, 0);
+    float roughness = 0.0f;
+    unsigned bits = 0u;
     GBits g{ &p.bn };
-    f3 accum = mk(0, 0, 0);
     unsigned slot = 0;
     bool alive = false;
     for (;;) {
@@ -568,14 +648,13 @@ __global__ __launch_bounds__(kTraceBlock, kMinWaves<PROG>) void pt_cont(TraceArg
         if (more && (ndead >= a.cont_refill || ndead == 64u)) {   // (wave-uniform: every lane is here)
             unsigned base = 0;
             if (lane == 0) base = atomicAdd(head, ndead);
-            base = __shfl(base, 0, 64);
+            base = __builtin_amdgcn_readfirstlane(base);   // (lane 0's: every lane is here)
             if (base + ndead >= n) more = false;
             if (!alive) {
-                const unsigned q = base + (unsigned)__popcll(dead & below);
+                const unsigned q = base + lanesBelow(dead);
                 if (q < n) {
                     slot = a.cont_perm ? a.cont_perm[q] : q;
-                    contLoad(a, slot, p, s);
-                    accum = mk(0, 0, 0);
+                    contLoad(a, slot, p, mask, roughness, bits);
                     alive = true;
                 }
             }
@@ -584,10 +663,24 @@ __global__ __launch_bounds__(kTraceBlock, kMinWaves<PROG>) void pt_cont(TraceArg
             if (!more) break;
             continue;
         }
-        if (alive && !bounceStep<PROG, false, kTraceBlock>(a, p, s, g, accum, lds_stack, lane, deep, cnt)) {
-            const unsigned aux = a.cont_aux[slot];
-            radianceOut(a, (long long)(aux & 0x7fffffffu), max3s(accum, 0.0f), g.sharp(), (aux >> 31) != 0u);
-            alive = false;
+        // the radiance is only ever assigned by the step that ends the path (contStore): zero until then, so
+        // it is no state of the loop's
+        f3 accum = mk(0, 0, 0);
+        if (alive) {
+            PState s;
+            s.mask = mask;
+            // what the variant knows of the record: without PBR code nothing ever assigns the roughness
+            s.roughness = kHasTex<PROG> ? roughness : 0.0f;
+            pathBitsTo(s, bits);
+            const bool go = bounceStep<PROG, false, kTraceBlock, kWaveBaseOf<PROG>>(a, p, s, g, accum, lds_stack, lane, deep, cnt);
+            mask = s.mask; roughness = s.roughness;
+            bits = pathBitsOf(s);
+            if (kWaveBaseOf<PROG>) asm volatile("" : "+v"(bits));   // (carried as the word, not as its six fields)
+            if (!go) {
+                const unsigned aux = a.cont_aux[slot];
+                radianceOut(a, (long long)(aux & 0x7fffffffu), max3s(accum, 0.0f), g.sharp(), (aux >> 31) != 0u);
+                alive = false;
+            }
         }
     }
 }
@@ -651,7 +744,7 @@ __global__ __launch_bounds__(kBlock, kMinWaves<PROG>) void pt_persist(TraceArgs 
             if (next >= end) break;
             continue;
         }
-        if (alive && !bounceStep<PROG, COUNT, kBlock>(a, p, s, g, accum, lds_stack, tid, deep, cnt)) {
+        if (alive && !bounceStep<PROG, COUNT, kBlock, false>(a, p, s, g, accum, lds_stack, tid, deep, cnt)) {
             const f3 r = max3s(accum, 0.0f);
             w.gb0[pix] = make_float4(g.nrm.x, g.nrm.y, g.nrm.z, g.id);
             w.gb1[pix] = make_float4(g.col.x, g.col.y, g.col.z, g.sharp);
