@@ -118,7 +118,7 @@ struct TraceArgs {
     float4* out;            // accumulation out
     // the megakernel: per pixel (py * width + px) CalculateRadiance()'s result and the pre-history
     // alpha flag (0, 1.01 or -1: the G-buffer sharpness and the 2x2 edge test); pt_blend folds in the
-    // history (js/PathTracingCommon.js:1326-1357), so the kernel never reads it and consecutive frames'
+    // history (pt_program.h historyBlend), so the kernel never reads it and consecutive frames'
     // path tracing may overlap
     float4* rad;
     // late-bounce compaction (megakernel mesh draws; pt_cont): after a bounce >= cont_bounce,
@@ -239,7 +239,7 @@ struct OutputArgs {
     OrderArgs ob;
 };
 
-// pt_blend: the progressive accumulation of a megakernel draw (js/PathTracingCommon.js:1326-1357) over
+// pt_blend: the progressive accumulation of a megakernel draw (pt_program.h historyBlend) over
 // the owned 16-row bands: out = history (x 0.5 when the camera moved, 0 at frame 1) + radiance, alpha
 // from the radiance's pre-history flag and the history's
 struct BlendArgs {

@@ -1,6 +1,6 @@
-// pt_device.h — device routines shared by the megakernel (pt_kernels.hip) and the wavefront
+// pt_device.h — device routines shared by the megakernel (pt_trace.h) and the wavefront
 // kernels (pt_wavefront.hip): the reference's random / sampling / material / intersection helpers
-// with the pinned GLSL semantics (pt_glsl.h). Each cites the GLSL it restates.
+// with the pinned GLSL semantics (pt_glsl.h), the lane and stack helpers. Each cites the GLSL it restates.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -102,6 +102,25 @@ PT_D unsigned laneNow()
     unsigned l;
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
     return l;
+}
+
+// Which pixel of its block a lane shades: lane bits (x0, y0, x1, x2, y1, y2) of an 8x8 block, which put every
+// GL 2x2 fragment quad into 4 consecutive lanes (quadEdge, pt_program.h), or (x0, y0, x1, y1) of part `part`
+// of a split tile's quadrant (pt_trace.h tracePlace)
+PT_D void placeLane(int part, int lane, int& lx, int& ly)
+{
+    if (part < 0) { lx = (lane & 1) | ((lane >> 1) & 6); ly = ((lane >> 1) & 1) | ((lane >> 3) & 6); }
+    else {
+        lx = (part & 1) * 4 + ((lane & 1) | ((lane >> 1) & 2));
+        ly = (part >> 1) * 4 + (((lane >> 1) & 1) | ((lane >> 2) & 2));
+    }
+}
+// the pixel of lane `lane` of wave `wave` (the 8x8 quadrant) of the 16x16 tile `tx` of band `band`
+PT_D int2 tilePixel(int tx, int band, int wave, int lane)
+{
+    int lx, ly;
+    placeLane(-1, lane, lx, ly);
+    return make_int2(tx * kTile + (wave & 1) * 8 + lx, band * kTile + (wave >> 1) * 8 + ly);
 }
 
 typedef float vf2 __attribute__((ext_vector_type(2)));

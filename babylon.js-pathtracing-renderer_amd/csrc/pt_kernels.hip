@@ -29,12 +29,7 @@
 #include "pt_device.h"
 #include "pt_glsl.h"
 #include "pt_program.h"
-#include "pt_trace.h"
-#ifdef PT_SECPROF
-#define PT_SECPROF_ON 1
-#else
-#define PT_SECPROF_ON 0
-#endif
+#include "pt_trace.h"   // kTraceBlock, kTraceSub (pt_launch_trace's grid), kCostBuckets (pt_trace's cost entries)
 
 using namespace ptg;
 
@@ -192,11 +187,10 @@ __global__ __launch_bounds__(256) void pt_copy(CopyArgs a)
 }
 
 // ------------------------------------------------------------------------------ accumulation
-// The history half of main() (js/PathTracingCommon.js:1326-1357) for a megakernel draw: the pixel's
-// history texel (previousBuffer = the screenCopy target), cleared at frame 1 and halved while the camera
-// moves, plus the radiance pt_trace left in `rad`; alpha = the radiance's pre-history flag unless the
-// history's says 1.01 (stays sharp) or -1 (0). Each pixel reads only its own texels, so `prev` may be
-// `out` (in-place history). A block covers 64 columns x one 16-row band, each thread 4 rows, loads first.
+// The history half of main() for a megakernel draw (pt_program.h historyBlend): the pixel's history texel
+// (previousBuffer = the screenCopy target) and the radiance and pre-history alpha pt_trace left in `rad`.
+// Each pixel reads only its own texels, so `prev` may be `out` (in-place history). A block covers 64
+// columns x one 16-row band, each thread 4 rows, loads first.
 PT_D void blendRows(const BlendArgs& a, int x, int r0)
 {
     typedef float nt4 __attribute__((ext_vector_type(4)));
@@ -214,17 +208,8 @@ PT_D void blendRows(const BlendArgs& a, int x, int r0)
     for (int k = 0; k < 4; k++) {
         const int y = r0 + 4 * k;
         if (y >= a.height) break;
-        float4 prev = make_float4(pv[k].x, pv[k].y, pv[k].z, pv[k].w);
-        float cr = rv[k].x, cg = rv[k].y, cb = rv[k].z, ca = rv[k].w;
-        if (a.frame == 1.0f) prev = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        else if (a.moving) {
-            prev.x *= 0.5f; prev.y *= 0.5f; prev.z *= 0.5f;
-            cr *= 0.5f; cg *= 0.5f; cb *= 0.5f;
-            prev.w = 0.0f;
-        }
-        if (prev.w == 1.01f) ca = 1.01f;
-        if (prev.w == -1.0f) ca = 0.0f;
-        a.out[(long long)y * a.width + x] = make_float4(prev.x + cr, prev.y + cg, prev.z + cb, ca);
+        a.out[(long long)y * a.width + x] = historyBlend(make_float4(pv[k].x, pv[k].y, pv[k].z, pv[k].w),
+                                                         mk(rv[k].x, rv[k].y, rv[k].z), rv[k].w, a.frame, a.moving);
     }
 }
 // The draw's record counter and pt_cont's queue head (threads 0 and 1 of the first workgroup; pt_cont is

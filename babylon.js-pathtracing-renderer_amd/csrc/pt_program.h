@@ -1,7 +1,9 @@
-// pt_program.h — the per-path part of the reference's fragment program, shared by the megakernel
-// (pt_kernels.hip: pt_trace, pt_persist) and the wavefront kernels (pt_wavefront.hip): the hit
-// record, CalculateRadiance's loop body after SceneIntersect (shadeStep), the physical sky and
-// main()'s camera ray. Everything keeps the pinned GLSL semantics of pt_glsl.h.
+// pt_program.h — the reference's fragment program, one statement of each step for the megakernel
+// (pt_trace.h: pt_trace, pt_cont, pt_persist), the wavefront kernels (pt_wavefront.hip) and the
+// accumulation (pt_kernels.hip): the hit record, the mesh hit's attributes (meshHit), CalculateRadiance's
+// loop body after SceneIntersect (shadeStep), the physical sky, and main()'s own steps - the camera ray,
+// the 2x2 edge test, the pre-history alpha, the history rule. Everything keeps the pinned GLSL
+// semantics of pt_glsl.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -9,6 +11,7 @@
 #include "pt_args.h"
 #include "pt_device.h"
 #include "pt_glsl.h"
+#include "pt_pathstate.h"
 #include "pt_quadric.h"
 
 namespace pt {
@@ -46,6 +49,20 @@ struct Cnt {
 #else
 #define PT_SEC(cnt, k) do {} while (0)
 #endif
+// a lane's counts of `paths` paths into the eight global counters (each path's camera ray read one
+// blue-noise texel)
+PT_D void countersFlush(const TraceArgs& a, const Cnt& cnt, unsigned paths)
+{
+    unsigned long long* C = a.counters;
+    if (paths) atomicAdd(&C[C_PATHS], (unsigned long long)paths);
+    atomicAdd(&C[C_SEGMENTS], (unsigned long long)cnt.seg);
+    atomicAdd(&C[C_NODE], (unsigned long long)cnt.node);
+    atomicAdd(&C[C_LEAF], (unsigned long long)cnt.leaf);
+    atomicAdd(&C[C_HIT], (unsigned long long)cnt.hit);
+    atomicAdd(&C[C_RGBA8], (unsigned long long)(cnt.tap + paths));
+    atomicAdd(&C[C_OVERFLOW], (unsigned long long)cnt.ovf);
+    atomicAdd(&C[C_HDR], (unsigned long long)cnt.hdr);
+}
 
 // CalculateRadiance's `out` parameters objectNormal / objectColor / objectID / pixelSharpness:
 // in registers (GOut) or, for the megakernel, packed (GOutLds): the normal and colour in LDS
@@ -173,6 +190,18 @@ PT_D void pathBegin(PState& s, G& g)
     s.diffuseCount = 0; s.hitType = -100; s.bounce = 0;
     s.coat = false; s.specular = true; s.sampleLight = false;
     g.clear();   // pinned `out` zeros
+}
+// PState's small integers and flags to and from their one-word form (pt_pathstate.h): the word of a
+// pt_cont record and of the wavefront queue, and the register that carries them across a BVH walk
+PT_D unsigned pathBitsOf(const PState& s)
+{
+    return pathBitsPack(s.diffuseCount, s.hitType, s.bounce, s.coat, s.specular, s.sampleLight);
+}
+PT_D void pathBitsTo(PState& s, unsigned bits)
+{
+    const PathBits b = pathBitsUnpack(bits);
+    s.diffuseCount = b.diffuseCount; s.hitType = b.hitType; s.bounce = b.bounce;
+    s.coat = b.coat; s.specular = b.specular; s.sampleLight = b.sampleLight;
 }
 
 // Get_Sky_Color (js/PathTracingCommon.js:416-475, the three.js SkyShader Preetham model). The
@@ -307,6 +336,36 @@ PT_D f3 envColor(const TraceArgs& a, f3 rd, Cnt& cnt)
     const float4 t = texBilinearF(a.hdr, u, v);
     if (COUNT) cnt.hdr += 4;
     return mk(t.x, t.y, t.z) * a.hdr_exposure;
+}
+
+// the mesh hit's attributes (js/GLTFModelPathTracing_FragmentShader.js:300-346): interpolated
+// normal and uv from the triangle texels 2-5, optional bump map, model transform
+template <int PROG, bool COUNT>
+PT_D void meshHit(const TraceArgs& a, float triID, float triU, float triV, Hit& h, Cnt& cnt)
+{
+    float4 v2 = fetch32(a.tri, a.tri_texels, triID + 2.0f), v3 = fetch32(a.tri, a.tri_texels, triID + 3.0f),
+           v4 = fetch32(a.tri, a.tri_texels, triID + 4.0f), v5 = fetch32(a.tri, a.tri_texels, triID + 5.0f);
+    if (COUNT) cnt.hit++;
+    float triW = 1.0f - triU - triV;
+    f3 nn = normalize(mk(v2.y, v2.z, v2.w) * triW + mk(v3.x, v3.y, v3.z) * triU + mk(v3.w, v4.x, v4.y) * triV);
+    h.u = triW * v4.z + triU * v5.x + triV * v5.z;
+    h.v = triW * v4.w + triU * v5.y + triV * v5.w;
+    if (kHasTex<PROG> && a.uses_bump) {   // perturbNormal(n, vec2(1), uv), js/GLTFModelPathTracing_FragmentShader.js:72-92
+        f3 S = onb_u(nn);
+        f3 T = cross(nn, S);
+        f3 N = normalize(nn);
+        if (dot(cross(S, T), N) < 0.0f) { S = S * -1.0f; T = T * -1.0f; }
+        float tx[4];
+        texBilinear(a.bump, h.u, h.v, tx);
+        if (COUNT) cnt.tap += 4;
+        f3 mN = normalize(mk(tx[0] * 2.0f - 1.0f, tx[1] * 2.0f - 1.0f, tx[2] * 2.0f - 1.0f));
+        mN.x *= 1.0f; mN.y *= 1.0f;
+        nn = normalize(S * mN.x + T * mN.y + N * mN.z);
+    }
+    h.normal = normalize(mul3t(a.model, nn));
+    h.type = a.uses_albedo ? PBR_MATERIAL : a.model_mat;
+    h.color = mk(1.0f, 1.0f, 1.0f);
+    h.id = meshObjectId<PROG>(a);
 }
 
 // The loop body after SceneIntersect, for the intersection `h` of the current ray. Returns false
@@ -495,5 +554,54 @@ PT_D void cameraRay(const TraceArgs& a, int px, int py, Path& p)
     p.ro = camPos + apert;
 }
 
+// main()'s 2x2 fine derivatives of the G-buffer and its edge test (js/PathTracingCommon.js:1306-1320). A
+// lane's quad partners are lanes ^1 (x) and ^2 (y) (placeLane), so every lane of the wave calls it, also
+// those without a pixel.
+PT_D bool quadEdge(f3 nrm, float id, f3 col, int lane)
+{
+    const bool xodd = lane & 1, yodd = lane & 2;
+    auto ddx = [&](float v) { float o = __shfl_xor(v, 1, 64); return xodd ? v - o : o - v; };
+    auto ddy = [&](float v) { float o = __shfl_xor(v, 2, 64); return yodd ? v - o : o - v; };
+    float dNx = fabsf(ddx(nrm.x)) + fabsf(ddy(nrm.x));
+    float dNy = fabsf(ddx(nrm.y)) + fabsf(ddy(nrm.y));
+    float dNz = fabsf(ddx(nrm.z)) + fabsf(ddy(nrm.z));
+    float normalDiff = gsmoothstep(0.2f, 0.6f, dNx) + gsmoothstep(0.2f, 0.6f, dNy) + gsmoothstep(0.2f, 0.6f, dNz);
+    float dObj = fabsf(ddx(id)) > 0.0f ? 1.0f : 0.0f;
+    dObj += fabsf(ddy(id)) > 0.0f ? 1.0f : 0.0f;
+    float objectDiff = gsmoothstep(0.0f, 0.5f, dObj);
+    f3 dcx = mk(ddx(col.x), ddx(col.y), ddx(col.z));
+    f3 dcy = mk(ddy(col.x), ddy(col.y), ddy(col.z));
+    float dCol = length(dcx) > 0.0f ? 1.0f : 0.0f;
+    dCol += length(dcy) > 0.0f ? 1.0f : 0.0f;
+    float colorDiff = gsmoothstep(0.0f, 0.5f, dCol);
+    return colorDiff >= 1.0f || normalDiff >= 1.0f || objectDiff >= 1.0f;
+}
+
+// main()'s alpha before the history (js/PathTracingCommon.js:1339-1349), from the G-buffer sharpness and
+// the edge test: the first three of the reference's five `currentPixel.a` assignments
+PT_D float alphaOf(float sharp, bool edge)
+{
+    float ca = 0.0f;
+    if (edge) sharp = 1.01f;
+    if (sharp == 1.01f) ca = 1.01f;
+    if (sharp == -1.0f) ca = -1.0f;
+    return ca;
+}
+
+// main()'s history rule (js/PathTracingCommon.js:1326-1337, 1352-1357): the history texel cleared at frame 1
+// and halved with the radiance while the camera moves, the two alpha assignments that read the history,
+// the sum. `r` = the pixel's radiance, `ca` = alphaOf.
+PT_D float4 historyBlend(float4 prev, f3 r, float ca, float frame, bool moving)
+{
+    if (frame == 1.0f) prev = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    else if (moving) {
+        prev.x *= 0.5f; prev.y *= 0.5f; prev.z *= 0.5f;
+        r.x *= 0.5f; r.y *= 0.5f; r.z *= 0.5f;
+        prev.w = 0.0f;
+    }
+    if (prev.w == 1.01f) ca = 1.01f;
+    if (prev.w == -1.0f) ca = 0.0f;
+    return make_float4(prev.x + r.x, prev.y + r.y, prev.z + r.z, ca);
+}
 
 } // namespace pt

@@ -9,7 +9,6 @@
 #include "pt_args.h"
 #include "pt_device.h"
 #include "pt_glsl.h"
-#include "pt_pathstate.h"
 #include "pt_program.h"
 #ifdef PT_SECPROF
 #define PT_SECPROF_ON 1
@@ -69,36 +68,6 @@ struct MegaStack {
         return true;
     }
 };
-
-// the mesh hit's attributes (js/GLTFModelPathTracing_FragmentShader.js:300-346): interpolated
-// normal and uv from the triangle texels 2-5, optional bump map, model transform
-template <int PROG, bool COUNT>
-PT_D void meshHit(const TraceArgs& a, float triID, float triU, float triV, Hit& h, Cnt& cnt)
-{
-    float4 v2 = fetch32(a.tri, a.tri_texels, triID + 2.0f), v3 = fetch32(a.tri, a.tri_texels, triID + 3.0f),
-           v4 = fetch32(a.tri, a.tri_texels, triID + 4.0f), v5 = fetch32(a.tri, a.tri_texels, triID + 5.0f);
-    if (COUNT) cnt.hit++;
-    float triW = 1.0f - triU - triV;
-    f3 nn = normalize(mk(v2.y, v2.z, v2.w) * triW + mk(v3.x, v3.y, v3.z) * triU + mk(v3.w, v4.x, v4.y) * triV);
-    h.u = triW * v4.z + triU * v5.x + triV * v5.z;
-    h.v = triW * v4.w + triU * v5.y + triV * v5.w;
-    if (kHasTex<PROG> && a.uses_bump) {   // perturbNormal(n, vec2(1), uv), js/GLTFModelPathTracing_FragmentShader.js:72-92
-        f3 S = onb_u(nn);
-        f3 T = cross(nn, S);
-        f3 N = normalize(nn);
-        if (dot(cross(S, T), N) < 0.0f) { S = S * -1.0f; T = T * -1.0f; }
-        float tx[4];
-        texBilinear(a.bump, h.u, h.v, tx);
-        if (COUNT) cnt.tap += 4;
-        f3 mN = normalize(mk(tx[0] * 2.0f - 1.0f, tx[1] * 2.0f - 1.0f, tx[2] * 2.0f - 1.0f));
-        mN.x *= 1.0f; mN.y *= 1.0f;
-        nn = normalize(S * mN.x + T * mN.y + N * mN.z);
-    }
-    h.normal = normalize(mul3t(a.model, nn));
-    h.type = a.uses_albedo ? PBR_MATERIAL : a.model_mat;
-    h.color = mk(1.0f, 1.0f, 1.0f);
-    h.id = meshObjectId<PROG>(a);
-}
 
 // The analytic winner's object-space normal formed after the walk (the 8-wave mesh programs with the two
 // spheres): unitSphere's own expression over the same transformed ray and the same t - the walk leaves h.t as
@@ -190,18 +159,6 @@ PT_D void sceneIntersect(const TraceArgs& a, f3 rayO, f3 rayD, Hit& h, float2* l
         analyticAttributes<PROG>(a, h, sn);
     }
     PT_SEC(cnt, 3);
-}
-
-// PState's small integers and flags to and from their one-word form (pt_pathstate.h)
-PT_D unsigned pathBitsOf(const PState& s)
-{
-    return pathBitsPack(s.diffuseCount, s.hitType, s.bounce, s.coat, s.specular, s.sampleLight);
-}
-PT_D void pathBitsTo(PState& s, unsigned bits)
-{
-    const PathBits b = pathBitsUnpack(bits);
-    s.diffuseCount = b.diffuseCount; s.hitType = b.hitType; s.bounce = b.bounce;
-    s.coat = b.coat; s.specular = b.specular; s.sampleLight = b.sampleLight;
 }
 
 // One iteration of CalculateRadiance's loop: SceneIntersect, then the shading step
@@ -356,19 +313,14 @@ PT_D f3 radiance(const TraceArgs& a, Path& p, G& g, float2* lds, unsigned lane_s
     return max3s(accum, 0.0f);
 }
 
-// what main() computes of pixel `pi` without the history (js/PathTracingCommon.js:1304-1349): the
-// radiance r and the alpha flag from the G-buffer sharpness and the 2x2 edge test - the first three of
-// the reference's five `currentPixel.a` assignments (:1339, :1347, :1349); pt_blend applies the two
-// that read the history (:1352, :1355) and the blend itself (:1326-1337, :1357). Streamed once per
-// frame: a non-temporal store, so that it displaces fewer BVH records in L2.
+// what main() computes of pixel `pi` without the history: the radiance r and the alpha flag from the
+// G-buffer sharpness and the 2x2 edge test (pt_program.h alphaOf); pt_blend applies the history rule
+// (historyBlend). Streamed once per frame: a non-temporal store, so that it displaces fewer BVH records
+// in L2.
 PT_D void radianceOut(const TraceArgs& a, long long pi, f3 r, float sharp, bool edge)
 {
-    float ca = 0.0f;
-    if (edge) sharp = 1.01f;
-    if (sharp == 1.01f) ca = 1.01f;
-    if (sharp == -1.0f) ca = -1.0f;
     typedef float nt4 __attribute__((ext_vector_type(4)));
-    const nt4 o = { r.x, r.y, r.z, ca };
+    const nt4 o = { r.x, r.y, r.z, alphaOf(sharp, edge) };
     __builtin_nontemporal_store(o, (nt4*)&a.rad[pi]);
 }
 
@@ -388,8 +340,6 @@ PT_D unsigned lanesBelow(unsigned long long mask)
 {
     return __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
 }
-
-PT_D float xorq(float v, int m) { return __shfl_xor(v, m, 64); }
 
 // longest-first dispatch: wave durations (shader clock) in 8 log-scale buckets per octave (pt_order_build)
 constexpr int kCostBuckets = 128;
@@ -415,17 +365,8 @@ constexpr int kTraceSub = 4;   // workgroups per 16x16 tile
 struct TracePlace {
     int px, py, part;
     unsigned costIdx;
-    int x0, y0;   // the wave's block (8x8, or a split tile's quadrant): wave-uniform, (px, py) = (x0, y0) + placeLane
+    int x0, y0;   // the wave's block (8x8, or a split tile's quadrant): wave-uniform, (px, py) = (x0, y0) + placeLane (pt_device.h)
 };
-// lane bits (x0, y0, x1, x2, y1, y2) of an 8x8 block, or (x0, y0, x1, y1) of part `part` of a split tile's quadrant
-PT_D void placeLane(int part, int lane, int& lx, int& ly)
-{
-    if (part < 0) { lx = (lane & 1) | ((lane >> 1) & 6); ly = ((lane >> 1) & 1) | ((lane >> 3) & 6); }
-    else {
-        lx = (part & 1) * 4 + ((lane & 1) | ((lane >> 1) & 2));
-        ly = (part >> 1) * 4 + (((lane >> 1) & 1) | ((lane >> 2) & 2));
-    }
-}
 PT_D bool tracePlace(const TraceArgs& a, int lane, TracePlace& pl)
 {
     int wave, part = -1;
@@ -551,22 +492,7 @@ __global__ __launch_bounds__(kTraceBlock, kMinWaves<PROG>) void pt_trace(TraceAr
         return c;
     });
 
-    // ---- 2x2 fine derivatives (js/PathTracingCommon.js:1306-1320): partner lanes ^1 (x) and ^2 (y)
-    const bool xodd = lane & 1, yodd = lane & 2;
-    auto ddx = [&](float v) { float o = xorq(v, 1); return xodd ? v - o : o - v; };
-    auto ddy = [&](float v) { float o = xorq(v, 2); return yodd ? v - o : o - v; };
-    float dNx = fabsf(ddx(g.nrm.x)) + fabsf(ddy(g.nrm.x));
-    float dNy = fabsf(ddx(g.nrm.y)) + fabsf(ddy(g.nrm.y));
-    float dNz = fabsf(ddx(g.nrm.z)) + fabsf(ddy(g.nrm.z));
-    float normalDiff = gsmoothstep(0.2f, 0.6f, dNx) + gsmoothstep(0.2f, 0.6f, dNy) + gsmoothstep(0.2f, 0.6f, dNz);
-    float dObj = fabsf(ddx(g.id)) > 0.0f ? 1.0f : 0.0f;
-    dObj += fabsf(ddy(g.id)) > 0.0f ? 1.0f : 0.0f;
-    float objectDiff = gsmoothstep(0.0f, 0.5f, dObj);
-    f3 dcx = mk(ddx(g.col.x), ddx(g.col.y), ddx(g.col.z));
-    f3 dcy = mk(ddy(g.col.x), ddy(g.col.y), ddy(g.col.z));
-    float dCol = length(dcx) > 0.0f ? 1.0f : 0.0f;
-    dCol += length(dcy) > 0.0f ? 1.0f : 0.0f;
-    float colorDiff = gsmoothstep(0.0f, 0.5f, dCol);
+    const bool edge = quadEdge(g.nrm, g.id, g.col, lane);   // (every lane: the quad's helpers too)
 
 #ifdef PT_SECPROF
     if (!COUNT && a.wave_log) {   // wave timeline in wall-clock ticks (100 MHz), one slot per workgroup
@@ -589,24 +515,13 @@ __global__ __launch_bounds__(kTraceBlock, kMinWaves<PROG>) void pt_trace(TraceAr
         atomicAdd(&a.counters[6], 1ull);
     }
 #endif
-    if (COUNT && active && !PT_SECPROF_ON) {
-        unsigned long long* C = a.counters;
-        atomicAdd(&C[C_PATHS], 1ull);
-        atomicAdd(&C[C_SEGMENTS], (unsigned long long)cnt.seg);
-        atomicAdd(&C[C_NODE], (unsigned long long)cnt.node);
-        atomicAdd(&C[C_LEAF], (unsigned long long)cnt.leaf);
-        atomicAdd(&C[C_HIT], (unsigned long long)cnt.hit);
-        atomicAdd(&C[C_RGBA8], (unsigned long long)(cnt.tap + 1));
-        atomicAdd(&C[C_OVERFLOW], (unsigned long long)cnt.ovf);
-        atomicAdd(&C[C_HDR], (unsigned long long)cnt.hdr);
-    }
+    if (COUNT && active && !PT_SECPROF_ON) countersFlush(a, cnt, 1u);
     if (a.cost && lane == 0) {   // this wave's duration, averaged with the tile's
         // history, for the next order (a split tile's four parts share their quadrant's entry)
         const unsigned long long dur = min(clock64() - t_start, 0xffffffffull);
         a.cost[pl.costIdx] = (unsigned)((dur + (unsigned long long)a.cost[pl.costIdx]) >> 1);
     }
     if (!active || px >= a.width || py >= a.height) return;   // quad helper outside the target, idle lane
-    const bool edge = colorDiff >= 1.0f || normalDiff >= 1.0f || objectDiff >= 1.0f;
     const long long pi = (long long)py * a.width + px;
     if (FEAT || (COUNT && a.feat0)) featureOut(a, pi, g);
     if (CONT && slot >= 0) {   // the path continues in pt_cont, which writes the pixel's radiance
@@ -724,10 +639,8 @@ __global__ __launch_bounds__(kBlock, kMinWaves<PROG>) void pt_persist(TraceArgs 
                     const unsigned per_band = (unsigned)tiles_x * 4u;
                     const unsigned bl = L / per_band, rem = L - bl * per_band;
                     const unsigned tx = rem >> 2, sub = rem & 3u;
-                    const int band = (int)bl * a.num_parts + a.part;
-                    const int lx = (int)((l & 1u) | ((l >> 1) & 6u)), ly = (int)(((l >> 1) & 1u) | ((l >> 3) & 6u));
-                    const int px = (int)tx * kTile + (int)(sub & 1u) * 8 + lx;
-                    const int py = band * kTile + (int)(sub >> 1) * 8 + ly;
+                    const int2 xy = tilePixel((int)tx, (int)bl * a.num_parts + a.part, (int)sub, (int)l);
+                    const int px = xy.x, py = xy.y;
                     if (px < w.wq && py < w.hq) {
                         cameraRay(a, px, py, p);
                         pathBegin(s, g);
@@ -752,17 +665,7 @@ __global__ __launch_bounds__(kBlock, kMinWaves<PROG>) void pt_persist(TraceArgs 
             alive = false;
         }
     }
-    if (COUNT) {
-        unsigned long long* C = a.counters;
-        if (paths) atomicAdd(&C[C_PATHS], (unsigned long long)paths);
-        atomicAdd(&C[C_SEGMENTS], (unsigned long long)cnt.seg);
-        atomicAdd(&C[C_NODE], (unsigned long long)cnt.node);
-        atomicAdd(&C[C_LEAF], (unsigned long long)cnt.leaf);
-        atomicAdd(&C[C_HIT], (unsigned long long)cnt.hit);
-        atomicAdd(&C[C_RGBA8], (unsigned long long)(cnt.tap + paths));
-        atomicAdd(&C[C_OVERFLOW], (unsigned long long)cnt.ovf);
-        atomicAdd(&C[C_HDR], (unsigned long long)cnt.hdr);
-    }
+    if (COUNT) countersFlush(a, cnt, paths);
 }
 
 } // namespace pt

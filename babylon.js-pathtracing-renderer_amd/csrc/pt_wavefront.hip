@@ -1,4 +1,5 @@
-// pt_wavefront.hip — the wavefront form of the path-tracing program (the default backend).
+// pt_wavefront.hip — the wavefront form of the path-tracing program (a queued backend; the megakernel,
+// pt_trace.h, is the default one).
 //
 // The GLSL runs one fragment = one whole path (<= 6 segments); on a 64-lane wave that leaves most
 // lanes idle: paths end at different bounces, branch into different materials, and a few lanes
@@ -6,19 +7,21 @@
 // is cut at its segment boundaries and every segment stage runs as its own kernel over a compacted
 // queue of live paths:
 //
-//   wf_raygen            main() up to SetupScene (js/PathTracingCommon.js:1259-1292): camera ray,
-//                        seeds, blue-noise texel; every pixel of the owned bands -> queue 0
+//   wf_raygen            main() up to SetupScene (cameraRay: camera ray, seeds, blue-noise texel);
+//                        every pixel of the owned bands -> queue 0
 //   per bounce b = 0..5:
 //     wf_extend   <P>    SceneIntersect's analytic part (2 spheres, 6 quads) + the BVH root-box test;
 //                        rays that enter the model's root box are appended to the BVH queue
-//     wf_bvh      <P>    the BVH walk (js/GLTFModelPathTracing_FragmentShader.js:201-344) only for
-//                        those rays: every lane of a wave traverses
+//     wf_bvh      <P>    the BVH walk and the mesh hit's attributes (meshHit) only for those rays:
+//                        every lane of a wave traverses
 //     wf_shade    <P>    one iteration of CalculateRadiance's loop body; surviving paths are appended
 //                        to queue b+1 (wave ballots + block prefix + one atomic per block-iteration
 //                        on the shard's counter: kShards counters, never one hot word)
-//   wf_finish            main() after CalculateRadiance: 2x2-quad derivatives + accumulation
+//   wf_finish            main() after CalculateRadiance: the 2x2 edge test, the alpha, the history rule
 //
-// Path state travels with the queue as four 16-byte SoA records (coalesced dwordx4 loads/stores);
+// Path state travels with the queue as four 16-byte SoA records (coalesced dwordx4 loads/stores:
+// A = origin, pixel | B = direction, blue-noise counter | C = mask, roughness | D = seeds, the state
+// word of pt_pathstate.h, the blue-noise bytes);
 // per-pixel outputs (G-buffer for the derivatives, radiance) are pixel-indexed. Every path performs
 // exactly the GLSL's sequence of IEEE ops and random draws, only the schedule differs, so the
 // result is bit-identical to the oracle and to the megakernel (tests/test_gpu_parity.py).
@@ -31,16 +34,6 @@
 #include "pt_program.h"
 
 namespace pt {
-
-enum Flag : unsigned {
-    F_DIFFUSE_MASK = 7u,     // diffuseCount (0..6)
-    F_COAT = 1u << 3,        // coatTypeIntersected
-    F_SPECULAR = 1u << 4,    // bounceIsSpecular
-    F_SAMPLE_LIGHT = 1u << 5,
-    F_TYPE_SHIFT = 8,        // bits 8..15: previousIntersecType + 128 (after the PBR remap)
-};
-constexpr unsigned kTypeBias = 128u;
-
 
 PT_D float u2f(unsigned u) { return __uint_as_float(u); }
 PT_D unsigned f2u(float f) { return __float_as_uint(f); }
@@ -82,44 +75,16 @@ template <bool COUNT>
 __global__ __launch_bounds__(kBlock) void wf_raygen(TraceArgs a, WfBufs w)
 {
     const unsigned tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int lx = (lane & 1) | ((lane >> 1) & 6);
-    const int ly = ((lane >> 1) & 1) | ((lane >> 3) & 6);
-    const int band = blockIdx.y * a.num_parts + a.part;
-    const int px = blockIdx.x * kTile + (wave & 1) * 8 + lx;
-    const int py = band * kTile + (wave >> 1) * 8 + ly;
+    const int2 xy = tilePixel(blockIdx.x, blockIdx.y * a.num_parts + a.part, tid >> 6, tid & 63);
+    const int px = xy.x, py = xy.y;
     const bool active = px < w.wq && py < w.hq;
     Path p;
-    p.s0 = p.s1 = 0;
+    p.s0 = p.s1 = p.bn = 0;
     p.ro = p.rd = mk(0, 0, 0);
-    unsigned bnb = 0, pix = 0;
+    unsigned pix = 0;
     if (active) {
         pix = (unsigned)py * (unsigned)w.wq + (unsigned)px;
-        const float* m = a.cam.m;
-        f3 camRight = mk(m[0], m[1], m[2]), camUp = mk(m[4], m[5], m[6]), camFwd = mk(m[8], m[9], m[10]);
-        f3 camPos = mk(m[12], m[13], m[14]);
-        float fcx = (float)px + 0.5f, fcy = (float)py + 0.5f;
-        p.s0 = (uint32_t)a.frame * (uint32_t)fcx;
-        p.s1 = (uint32_t)(a.frame + 1.0f) * (uint32_t)fcy;
-        int bx = (int)gmod(fcx + floorf(a.rnd[0] * 256.0f), 256.0f);
-        int by = (int)gmod(fcy + floorf(a.rnd[1] * 256.0f), 256.0f);
-        if (bx < a.bluenoise.w && by < a.bluenoise.h) {
-            uchar4 b = a.bluenoise.p[by * a.bluenoise.w + bx];
-            bnb = (unsigned)b.x | ((unsigned)b.y << 8);
-        }
-        float ox = tentFilter(rng(p));
-        float oy = tentFilter(rng(p));
-        float ppx = ((fcx + ox) / a.res[0]) * 2.0f - 1.0f;
-        float ppy = ((fcy + oy) / a.res[1]) * 2.0f - 1.0f;
-        f3 rayDir = normalize((camRight * ppx) * a.ulen + (camUp * ppy) * a.vlen + camFwd);
-        f3 focal = rayDir * a.focus;
-        float ang = rng(p) * kTwoPi;
-        float rad = rng(p) * a.aperture;
-        float sn, cs;
-        gsincos(ang, sn, cs);
-        f3 apert = (camRight * cs + camUp * sn) * gsqrt(rad);
-        p.rd = normalize(focal - apert);
-        p.ro = camPos + apert;
+        cameraRay(a, px, py, p);
         // per-pixel outputs start at the `out` parameters' pinned zero
         w.gb0[pix] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         w.gb1[pix] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -132,9 +97,12 @@ __global__ __launch_bounds__(kBlock) void wf_raygen(TraceArgs a, WfBufs w)
     if (tid == 0) atomicAdd(&w.cnt[s], (unsigned)kBlock);
     w.qA[0][slot] = make_float4(p.ro.x, p.ro.y, p.ro.z, u2f(active ? pix : kHole));
     if (active) {
-        w.qB[0][slot] = make_float4(p.rd.x, p.rd.y, p.rd.z, -1.0f);   // blueNoise counter starts at -1
-        w.qC[0][slot] = make_float4(1.0f, 1.0f, 1.0f, 0.0f);           // mask, roughness
-        w.qD[0][slot] = make_float4(u2f(p.s0), u2f(p.s1), u2f(F_SPECULAR | ((kTypeBias - 100u) << F_TYPE_SHIFT)), u2f(bnb));
+        PState s0;
+        GOut g0;
+        pathBegin(s0, g0);
+        w.qB[0][slot] = make_float4(p.rd.x, p.rd.y, p.rd.z, pathCounter(p));   // -1: cameraRay leaves the counter bits 0
+        w.qC[0][slot] = make_float4(s0.mask.x, s0.mask.y, s0.mask.z, s0.roughness);
+        w.qD[0][slot] = make_float4(u2f(p.s0), u2f(p.s1), u2f(pathBitsOf(s0)), u2f(p.bn));
     }
     if (COUNT && active) { count_add<true>(a, C_PATHS, 1); count_add<true>(a, C_RGBA8, 1); }
 }
@@ -241,39 +209,19 @@ __global__ __launch_bounds__(kBlock, 4) void wf_bvh(TraceArgs a, WfBufs w, int b
         if (kTrail<PROG>) bvhWalkTrail<kRingOf<PROG>>(a, O, D, inv, dbl, rootT, hitT, (lds_float2*)lds, kBlock, tid, br);
         else if (kPairs<PROG>) bvhWalkPairs(a, O, D, inv, dbl, rootT, hitT, st, br);
         else bvhWalkRef(a, O, D, inv, dbl, c0, c1, rootT, hitT, st, br);
-        const unsigned nodes = br.nodes, leaves = br.leaves, ovf = br.ovf;
-        const bool lookup = br.lookup;
-        const float triID = br.triID, triU = br.triU, triV = br.triV;
-        unsigned taps = 0;
-        if (lookup) {
-            float4 v2 = fetch32(a.tri, a.tri_texels, triID + 2.0f), v3 = fetch32(a.tri, a.tri_texels, triID + 3.0f),
-                   v4 = fetch32(a.tri, a.tri_texels, triID + 4.0f), v5 = fetch32(a.tri, a.tri_texels, triID + 5.0f);
-            float triW = 1.0f - triU - triV;
-            f3 nn = normalize(mk(v2.y, v2.z, v2.w) * triW + mk(v3.x, v3.y, v3.z) * triU + mk(v3.w, v4.x, v4.y) * triV);
-            float hu = triW * v4.z + triU * v5.x + triV * v5.z;
-            float hv = triW * v4.w + triU * v5.y + triV * v5.w;
-            if (kHasTex<PROG> && a.uses_bump) {   // perturbNormal (js/GLTFModelPathTracing_FragmentShader.js:72-92)
-                f3 S = onb_u(nn);
-                f3 T = cross(nn, S);
-                f3 N = normalize(nn);
-                if (dot(cross(S, T), N) < 0.0f) { S = S * -1.0f; T = T * -1.0f; }
-                float tx[4];
-                texBilinear(a.bump, hu, hv, tx);
-                taps += 4;
-                f3 mN = normalize(mk(tx[0] * 2.0f - 1.0f, tx[1] * 2.0f - 1.0f, tx[2] * 2.0f - 1.0f));
-                mN.x *= 1.0f; mN.y *= 1.0f;
-                nn = normalize(S * mN.x + T * mN.y + N * mN.z);
-            }
-            f3 hn = normalize(mul3t(a.model, nn));
-            w.hit0[i] = make_float4(hitT, u2f((unsigned)meshObjectId<PROG>(a)), hu, hv);
-            w.hit1[i] = make_float4(hn.x, hn.y, hn.z, 0.0f);
+        Cnt cnt = { 0, 0, 0, 0, 0, 0, 0 };
+        if (br.lookup) {
+            Hit h;
+            meshHit<PROG, COUNT>(a, br.triID, br.triU, br.triV, h, cnt);
+            w.hit0[i] = make_float4(hitT, u2f((unsigned)h.id), h.u, h.v);
+            w.hit1[i] = make_float4(h.normal.x, h.normal.y, h.normal.z, 0.0f);
         }
         if (COUNT) {
-            count_add<true>(a, C_NODE, nodes);
-            count_add<true>(a, C_LEAF, leaves);
-            count_add<true>(a, C_HIT, lookup ? 1u : 0u);
-            count_add<true>(a, C_RGBA8, taps);
-            count_add<true>(a, C_OVERFLOW, ovf);
+            count_add<true>(a, C_NODE, br.nodes);
+            count_add<true>(a, C_LEAF, br.leaves);
+            count_add<true>(a, C_HIT, cnt.hit);
+            count_add<true>(a, C_RGBA8, cnt.tap);
+            count_add<true>(a, C_OVERFLOW, br.ovf);
         }
     }
 }
@@ -314,16 +262,13 @@ __global__ __launch_bounds__(kBlock) void wf_shade(TraceArgs a, WfBufs w, int b)
             p.ro = mk(A.x, A.y, A.z);
             p.rd = mk(B.x, B.y, B.z);
             p.s0 = f2u(D.x); p.s1 = f2u(D.y);
-            const unsigned flags = f2u(D.z);
             p.bn = f2u(D.w) & 0xffffu;
             setPathCounter(p, B.w);
             PState s;
             s.mask = mk(C.x, C.y, C.z);
             s.roughness = C.w;
-            s.diffuseCount = (int)(flags & F_DIFFUSE_MASK);
-            s.hitType = (int)((flags >> F_TYPE_SHIFT) & 255u) - (int)kTypeBias;
-            s.bounce = b;
-            s.coat = flags & F_COAT; s.specular = flags & F_SPECULAR; s.sampleLight = flags & F_SAMPLE_LIGHT;
+            pathBitsTo(s, f2u(D.z));
+            s.bounce = b;   // (the word's bounce byte, as the kernel's wave-uniform argument)
             // the hit record SceneIntersect would have returned (wf_extend + wf_bvh)
             Hit h;
             h.t = H0.x;
@@ -338,13 +283,10 @@ __global__ __launch_bounds__(kBlock) void wf_shade(TraceArgs a, WfBufs w, int b)
             Cnt cnt = { 0, 0, 0, 0, 0, 0, 0 };
             if (shadeStep<PROG, COUNT, GOutPix>(a, p, s, g, accum, h, cnt)) {
                 alive = true;
-                const unsigned nf = (unsigned)s.diffuseCount | (s.coat ? F_COAT : 0u) | (s.specular ? F_SPECULAR : 0u) |
-                                    (s.sampleLight ? F_SAMPLE_LIGHT : 0u) |
-                                    ((unsigned)(s.hitType + (int)kTypeBias) << F_TYPE_SHIFT);
                 oA = make_float4(p.ro.x, p.ro.y, p.ro.z, A.w);
                 oB = make_float4(p.rd.x, p.rd.y, p.rd.z, pathCounter(p));
                 oC = make_float4(s.mask.x, s.mask.y, s.mask.z, s.roughness);
-                oD = make_float4(u2f(p.s0), u2f(p.s1), u2f(nf), D.w);
+                oD = make_float4(u2f(p.s0), u2f(p.s1), u2f(pathBitsOf(s)), D.w);
             } else {
                 const f3 r = max3s(accum, 0.0f);
                 w.rad[pix] = make_float4(r.x, r.y, r.z, 0.0f);
@@ -365,51 +307,18 @@ __global__ __launch_bounds__(kBlock) void wf_shade(TraceArgs a, WfBufs w, int b)
 __global__ __launch_bounds__(kBlock) void wf_finish(TraceArgs a, WfBufs w)
 {
     const unsigned tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int lx = (lane & 1) | ((lane >> 1) & 6);
-    const int ly = ((lane >> 1) & 1) | ((lane >> 3) & 6);
-    const int band = blockIdx.y * a.num_parts + a.part;
-    const int px = blockIdx.x * kTile + (wave & 1) * 8 + lx;
-    const int py = band * kTile + (wave >> 1) * 8 + ly;
+    const int2 xy = tilePixel(blockIdx.x, blockIdx.y * a.num_parts + a.part, tid >> 6, tid & 63);
+    const int px = xy.x, py = xy.y;
     const bool active = px < w.wq && py < w.hq;
     float4 g0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), g1 = g0, r = g0;
     if (active) {
         const unsigned pix = (unsigned)py * (unsigned)w.wq + (unsigned)px;
         g0 = w.gb0[pix]; g1 = w.gb1[pix]; r = w.rad[pix];
     }
-    const bool xodd = lane & 1, yodd = lane & 2;
-    auto ddx = [&](float v) { float o = __shfl_xor(v, 1, 64); return xodd ? v - o : o - v; };
-    auto ddy = [&](float v) { float o = __shfl_xor(v, 2, 64); return yodd ? v - o : o - v; };
-    float dNx = fabsf(ddx(g0.x)) + fabsf(ddy(g0.x));
-    float dNy = fabsf(ddx(g0.y)) + fabsf(ddy(g0.y));
-    float dNz = fabsf(ddx(g0.z)) + fabsf(ddy(g0.z));
-    float normalDiff = gsmoothstep(0.2f, 0.6f, dNx) + gsmoothstep(0.2f, 0.6f, dNy) + gsmoothstep(0.2f, 0.6f, dNz);
-    float dObj = fabsf(ddx(g0.w)) > 0.0f ? 1.0f : 0.0f;
-    dObj += fabsf(ddy(g0.w)) > 0.0f ? 1.0f : 0.0f;
-    float objectDiff = gsmoothstep(0.0f, 0.5f, dObj);
-    f3 dcx = mk(ddx(g1.x), ddx(g1.y), ddx(g1.z));
-    f3 dcy = mk(ddy(g1.x), ddy(g1.y), ddy(g1.z));
-    float dCol = length(dcx) > 0.0f ? 1.0f : 0.0f;
-    dCol += length(dcy) > 0.0f ? 1.0f : 0.0f;
-    float colorDiff = gsmoothstep(0.0f, 0.5f, dCol);
+    const bool edge = quadEdge(mk(g0.x, g0.y, g0.z), g0.w, mk(g1.x, g1.y, g1.z), tid & 63);
     if (px >= a.width || py >= a.height) return;
     const long long pi = (long long)py * a.width + px;
-    float4 prev = a.prev[pi];
-    float cr = r.x, cg = r.y, cb = r.z, ca;
-    if (a.frame == 1.0f) prev = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    else if (a.moving) {
-        prev.x *= 0.5f; prev.y *= 0.5f; prev.z *= 0.5f;
-        cr *= 0.5f; cg *= 0.5f; cb *= 0.5f;
-        prev.w = 0.0f;
-    }
-    ca = 0.0f;
-    float sharp = g1.w;
-    if (colorDiff >= 1.0f || normalDiff >= 1.0f || objectDiff >= 1.0f) sharp = 1.01f;
-    if (sharp == 1.01f) ca = 1.01f;
-    if (sharp == -1.0f) ca = -1.0f;
-    if (prev.w == 1.01f) ca = 1.01f;
-    if (prev.w == -1.0f) ca = 0.0f;
-    a.out[pi] = make_float4(prev.x + cr, prev.y + cg, prev.z + cb, ca);
+    a.out[pi] = historyBlend(a.prev[pi], mk(r.x, r.y, r.z), alphaOf(g1.w, edge), a.frame, a.moving);
 }
 
 } // namespace pt
