@@ -5,19 +5,11 @@
 #include <stdint.h>
 
 #include "pt_glsl.h"
-#include "pt_plan.h"   // kBlock, kTile, kSplitParts, kOrderHeld, kSortBins: the constants the host's schedule shares
+#include "pt_plan.h"   // kBlock, kTile, kSplitParts, kOrderHeld, kSortBins, kStackLevels, kStackLds*, kShards, kTop*: the constants the host's schedule and layouts share
 
 namespace pt {
 
 constexpr int kWaveLogSlots = 13;   // experiment builds (PT_SECPROF): u64 per workgroup in TraceArgs::wave_log
-constexpr int kStackLevels = 28;     // stackLevels[28], js/GLTFModelPathTracing_FragmentShader.js:95
-// BVH stack levels kept in LDS per lane (deeper levels go to a global slab): 7 for the 4-wave variants;
-// the child-pair walk of the texture-free mesh programs runs at 8 waves/SIMD (pt_device.h kMinWaves),
-// where 6 LDS levels and the G-buffer fill the 160 KB of a CU (pt_trace.h MegaStack::push)
-constexpr int kStackLds = 7;
-constexpr int kStackLdsPairs = 6;
-constexpr int kStackLdsMin = kStackLdsPairs < kStackLds ? kStackLdsPairs : kStackLds;   // sizes the slab
-
 // child-pair record codes: a node's rank code from the build's rank pass (rank >= 0 of an inner
 // node, -1 - rank of a leaf) -> the 32-bit code the walk carries: the record's byte offset in the
 // one record array (inner records first, the leaf records from byte leafBase on), with kLeafBit set
@@ -27,13 +19,6 @@ __host__ __device__ inline uint32_t pairCode(float rankCode, uint32_t leafBase)
 {
     return rankCode >= 0.0f ? (uint32_t)rankCode * 64u : kLeafBit | (leafBase + (uint32_t)(-1.0f - rankCode) * 48u);
 }
-
-// restart-trail walk (pt_device.h bvhWalkTrail): one trail bit per depth 1..31 of a register; trees of
-// depth <= 28 (stackLevels[28] then never overflows); a jump table of the inner records at depths
-// 0..kTopLevels, by path, after the leaf records
-constexpr int kTrailMaxDepth = 28;
-constexpr int kTopLevels = 11;
-constexpr unsigned kTopEntries = (2u << kTopLevels) - 1u;   // 4095 record copies (64 B, 256 KB), heap order
 
 // the BVH walk of a mesh draw (TraceArgs::bvh_walk; the program variant's thousands digit, pt_device.h)
 enum { WALK_REF = 0, WALK_PAIRS = 1, WALK_TRAIL = 2 };
@@ -183,7 +168,6 @@ struct TraceArgs {
 // atomic per block-iteration on that shard's counter (no single hot word). Path state travels with
 // the queue as 4 x 16-byte SoA records, double-buffered between bounces; per-pixel outputs are
 // indexed py * wq + px.
-constexpr int kShards = 16;
 constexpr unsigned kHole = 0xFFFFFFFFu;   // queue-0 slot of a tile lane outside the frame
 
 struct WfBufs {

@@ -7,11 +7,23 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <string>
+
 #include "../../include/pt.h"
 
 struct Dev;
 struct DevTex;
 struct DevFx;
+
+enum TexKind { TEX_F32 = 0, TEX_U8 = 1, TEX_RT = 2 };   // RGBA32F data, RGBA8 data, RGBA32F render target
+
+// an error of `c`, a part (Dev) or a context (pt_ctx): both keep their last message in `err`
+template <class C> int fail(C* c, int code, const std::string& msg) { if (c) c->err = msg; return code; }
+template <class C> int hipfail(C* c, hipError_t e, const char* what)
+{
+    return fail(c, PT_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+#define HIPCHK(c, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return hipfail(c, e_, #call); } while (0)
 
 Dev* dev_ctx_create(int device, int* err);
 void dev_ctx_destroy(Dev* c);

@@ -525,8 +525,8 @@ PT_D void bvhWalkRef(const TraceArgs& a, f3 O, f3 D, f3 inv, bool dbl, float4 c0
     }
 }
 
-// Child-pair records (pt_pairs_* in pt_kernels.hip; only for trees whose links are exact in-range
-// integers, see pt_capi.cpp ensure_pairs). Nodes are addressed by a 32-bit code (pairCode,
+// Child-pair records (pt_pairs_* in pt_pairs.hip; only for trees whose links are exact in-range
+// integers, see pairs_build there). Nodes are addressed by a 32-bit code (pairCode,
 // pt_args.h): the byte offset of an inner node's record in the dense inner-record array, or
 // kLeafBit | the byte offset of a leaf's record in the dense leaf-record array, kept as float bits
 // in records and stack entries. Both arrays are read through buffer descriptors, so an inner code

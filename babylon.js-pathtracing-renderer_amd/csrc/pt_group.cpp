@@ -20,6 +20,7 @@
 // With one part (pt_ctx_create) every call is a plain forward to that part.
 #include "../../include/pt.h"
 #include "pt_dev.h"
+#include "pt_plan.h"   // kTile, the row-band height, and bands_owned
 
 #include <hip/hip_runtime.h>
 
@@ -30,11 +31,6 @@
 #include <string>
 #include <unordered_map>
 #include <vector>
-
-namespace {
-constexpr int kBand = 16;   // row-band height (pt_args.h kTile)
-enum Kind { K_F32 = 0, K_U8 = 1, K_RT = 2 };
-}  // namespace
 
 struct pt_texture;
 
@@ -59,7 +55,7 @@ struct pt_ctx {
 struct pt_texture {
     pt_ctx* ctx = nullptr;
     std::vector<DevTex*> sub;
-    int kind = K_F32;
+    int kind = TEX_F32;
     int w = 0, h = 0;
 };
 
@@ -72,12 +68,6 @@ struct pt_effect {
 
 namespace {
 
-int fail(pt_ctx* c, int code, const std::string& msg)
-{
-    if (c) c->err = msg;
-    return code;
-}
-
 // a part's error -> the context's message
 int take(pt_ctx* c, int k, int rc)
 {
@@ -85,16 +75,27 @@ int take(pt_ctx* c, int k, int rc)
     return rc;
 }
 
-int hipfail(pt_ctx* c, hipError_t e, const char* what)
+// a call forwarded to every part: f(k) is part k's, the first error ends it
+template <class F>
+int each(pt_ctx* c, F f)
 {
-    return fail(c, PT_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    for (int k = 0; k < c->n(); k++)
+        if (int rc = take(c, k, f(k))) return rc;
+    return PT_OK;
 }
 
-#define GHIP(c, call)                                      \
-    do {                                                   \
-        hipError_t e_ = (call);                            \
-        if (e_ != hipSuccess) return hipfail(c, e_, #call); \
-    } while (0)
+// ... and a reader of N numbers per part, summed over the parts
+template <int N, class T>
+int sum_parts(pt_ctx* c, T* out, int (*read)(Dev*, T*))
+{
+    std::fill(out, out + N, T(0));
+    return each(c, [&](int k) {
+        T v[N];
+        const int rc = read(c->parts[k], v);
+        for (int i = 0; i < N && !rc; i++) out[i] += v[i];
+        return rc;
+    });
+}
 
 bool is_trace(int prog)
 {
@@ -111,7 +112,7 @@ hipError_t copy_band_rows(char* dst, const char* src, size_t rowbytes, int N, in
                           int H, hipMemcpyKind kind, hipStream_t s, int dst_dev = -1, int src_dev = -1)
 {
     if (count <= 0) return hipSuccess;
-    auto row0 = [&](int m) { return (long)(b0 + (long)m * N) * kBand + off; };
+    auto row0 = [&](int m) { return (long)(b0 + (long)m * N) * pt::kTile + off; };
     if (dst_dev >= 0) {
         hipError_t e = hipSuccess;
         for (int m = 0; m < count && e == hipSuccess; m++) {
@@ -127,7 +128,7 @@ hipError_t copy_band_rows(char* dst, const char* src, size_t rowbytes, int N, in
     while (hi >= lo && row0(hi) + nrows > H) hi--;
     hipError_t e = hipSuccess;
     if (lo <= hi) {
-        const size_t pitch = (size_t)N * kBand * rowbytes;
+        const size_t pitch = (size_t)N * pt::kTile * rowbytes;
         const size_t at = (size_t)row0(lo) * rowbytes;
         e = hipMemcpy2DAsync(dst + at, pitch, src + at, pitch, nrows * rowbytes, (size_t)(hi - lo + 1), kind, s);
     }
@@ -140,18 +141,16 @@ hipError_t copy_band_rows(char* dst, const char* src, size_t rowbytes, int N, in
     return e;
 }
 
-int bands_of(int nb, int N, int k) { return k < nb ? (nb - k + N - 1) / N : 0; }
-
 int wait(pt_ctx* c, int k, hipEvent_t e, bool recorded)
 {
-    if (recorded) GHIP(c, hipStreamWaitEvent(dev_stream(c->parts[k]), e, 0));
+    if (recorded) HIPCHK(c, hipStreamWaitEvent(dev_stream(c->parts[k]), e, 0));
     return PT_OK;
 }
 
 int record(pt_ctx* c, int k, hipEvent_t e)
 {
-    GHIP(c, hipSetDevice(dev_device(c->parts[k])));
-    GHIP(c, hipEventRecord(e, dev_stream(c->parts[k])));
+    HIPCHK(c, hipSetDevice(dev_device(c->parts[k])));
+    HIPCHK(c, hipEventRecord(e, dev_stream(c->parts[k])));
     return PT_OK;
 }
 
@@ -164,23 +163,22 @@ int render_output_parts(pt_effect* fx, pt_texture* target)
     pt_texture* acc = it == fx->bound.end() ? nullptr : it->second;
     for (int j = 0; j < N; j++) {
         Dev* d = c->parts[j];
-        GHIP(c, hipSetDevice(dev_device(d)));
+        HIPCHK(c, hipSetDevice(dev_device(d)));
         const int lo = (j + N - 1) % N, hi = (j + 1) % N;
         if (int rc = wait(c, j, c->ev_draw[lo], c->has_draw[lo])) return rc;
         if (int rc = wait(c, j, c->ev_draw[hi], c->has_draw[hi])) return rc;
         if (!target)   // the previous gather read this part's canvas
             if (int rc = wait(c, j, c->ev_gather, c->has_gather)) return rc;
-        if (acc && acc->kind != K_U8) {
+        if (acc && acc->kind != TEX_U8) {
             // rows 2 below / 2 above each owned band, from the parts that own those bands
-            const int nb = (acc->h + kBand - 1) / kBand;
             const size_t rb = (size_t)acc->w * 16;
             char* dst = (char*)dev_texture_device_ptr(acc->sub[j]);
-            const int cnt = bands_of(nb, N, j);
+            const int cnt = pt::bands_owned(acc->h, N, j);
             const int dd = c->peer ? -1 : c->devs[j];
-            GHIP(c, copy_band_rows(dst, (const char*)dev_texture_device_ptr(acc->sub[lo]), rb, N, j, cnt, -2, 2, acc->h,
-                                   hipMemcpyDefault, dev_stream(d), dd, c->devs[lo]));
-            GHIP(c, copy_band_rows(dst, (const char*)dev_texture_device_ptr(acc->sub[hi]), rb, N, j, cnt, kBand, 2, acc->h,
-                                   hipMemcpyDefault, dev_stream(d), dd, c->devs[hi]));
+            HIPCHK(c, copy_band_rows(dst, (const char*)dev_texture_device_ptr(acc->sub[lo]), rb, N, j, cnt, -2, 2, acc->h,
+                                     hipMemcpyDefault, dev_stream(d), dd, c->devs[lo]));
+            HIPCHK(c, copy_band_rows(dst, (const char*)dev_texture_device_ptr(acc->sub[hi]), rb, N, j, cnt, pt::kTile, 2, acc->h,
+                                     hipMemcpyDefault, dev_stream(d), dd, c->devs[hi]));
         }
         if (int rc = take(c, j, dev_render(fx->sub[j], target ? target->sub[j] : nullptr))) return rc;
         if (int rc = record(c, j, c->ev_out[j])) return rc;
@@ -189,42 +187,59 @@ int render_output_parts(pt_effect* fx, pt_texture* target)
     if (target) return PT_OK;
     // gather every part's bands of the RGBA8 canvas into part 0's
     Dev* d0 = c->parts[0];
-    GHIP(c, hipSetDevice(dev_device(d0)));
+    HIPCHK(c, hipSetDevice(dev_device(d0)));
     char* dst = (char*)dev_canvas_ptr(d0);
     int cw = c->cw, ch = c->ch;
     if (cw == 0 && ch == 0 && acc) { cw = acc->w; ch = acc->h; }
-    const int nb = (ch + kBand - 1) / kBand;
     for (int k = 1; k < N; k++) {
         if (int rc = wait(c, 0, c->ev_out[k], true)) return rc;
-        GHIP(c, copy_band_rows(dst, (const char*)dev_canvas_ptr(c->parts[k]), (size_t)cw * 4, N, k, bands_of(nb, N, k), 0,
-                               kBand, ch, hipMemcpyDefault, dev_stream(d0), c->peer ? -1 : c->devs[0], c->devs[k]));
+        HIPCHK(c, copy_band_rows(dst, (const char*)dev_canvas_ptr(c->parts[k]), (size_t)cw * 4, N, k, pt::bands_owned(ch, N, k), 0,
+                                 pt::kTile, ch, hipMemcpyDefault, dev_stream(d0), c->peer ? -1 : c->devs[0], c->devs[k]));
     }
     if (int rc = record(c, 0, c->ev_gather)) return rc;
     c->has_gather = true;
     return PT_OK;
 }
 
-template <class F>
-pt_texture* make_tex(pt_ctx* c, int kind, int w, int h, int* err, F create)
+// A texture or an effect of the context (pt_ctx::*all): one sub-object per part from create(part, &rc); a
+// part's failure destroys the ones made so far
+template <class T, class Sub, class F>
+T* make_parts(pt_ctx* c, std::set<T*> pt_ctx::*all, void (*destroy)(Sub*), int* err, F create)
 {
     if (err) *err = PT_OK;
     if (!c) { if (err) *err = PT_ERR_ARG; return nullptr; }
-    auto* t = new pt_texture();
-    t->ctx = c; t->kind = kind; t->w = w; t->h = h;
+    auto* t = new T();
+    t->ctx = c;
     for (int k = 0; k < c->n(); k++) {
         int rc = PT_OK;
-        DevTex* d = create(c->parts[k], &rc);
+        Sub* d = create(c->parts[k], &rc);
         if (!d) {
             take(c, k, rc);
-            for (auto* s : t->sub) dev_texture_destroy(s);
+            for (auto* s : t->sub) destroy(s);
             delete t;
             if (err) *err = rc ? rc : PT_ERR_HIP;
             return nullptr;
         }
         t->sub.push_back(d);
     }
-    c->textures.insert(t);
+    (c->*all).insert(t);
     return t;
+}
+
+template <class F>
+pt_texture* make_tex(pt_ctx* c, int kind, int w, int h, int* err, F create)
+{
+    pt_texture* t = make_parts(c, &pt_ctx::textures, dev_texture_destroy, err, create);
+    if (t) { t->kind = kind; t->w = w; t->h = h; }
+    return t;
+}
+
+template <class F>
+pt_effect* make_fx(pt_ctx* c, int* err, F create)
+{
+    pt_effect* fx = make_parts(c, &pt_ctx::effects, dev_effect_destroy, err, create);
+    if (fx) fx->prog = dev_effect_program(fx->sub[0]);
+    return fx;
 }
 }  // namespace
 
@@ -333,8 +348,7 @@ int pt_sync(pt_ctx* c)
 int pt_canvas_resize(pt_ctx* c, int w, int h)
 {
     if (!c) return PT_ERR_ARG;
-    for (int k = 0; k < c->n(); k++)
-        if (int rc = take(c, k, dev_canvas_resize(c->parts[k], w, h))) return rc;
+    if (int rc = each(c, [&](int k) { return dev_canvas_resize(c->parts[k], w, h); })) return rc;
     c->cw = w; c->ch = h;
     return PT_OK;
 }
@@ -375,49 +389,13 @@ int pt_set_stream(pt_ctx* c, void* stream)
 pt_effect* pt_effect_create(pt_ctx* c, const char* src, const char* const* un, int nu, const char* const* sn, int ns,
                             int* err)
 {
-    if (err) *err = PT_OK;
-    if (!c) { if (err) *err = PT_ERR_ARG; return nullptr; }
-    auto* fx = new pt_effect();
-    fx->ctx = c;
-    for (int k = 0; k < c->n(); k++) {
-        int rc = PT_OK;
-        DevFx* f = dev_effect_create(c->parts[k], src, un, nu, sn, ns, &rc);
-        if (!f) {
-            take(c, k, rc);
-            for (auto* g : fx->sub) dev_effect_destroy(g);
-            delete fx;
-            if (err) *err = rc;
-            return nullptr;
-        }
-        fx->sub.push_back(f);
-    }
-    fx->prog = dev_effect_program(fx->sub[0]);
-    c->effects.insert(fx);
-    return fx;
+    return make_fx(c, err, [&](Dev* d, int* e) { return dev_effect_create(d, src, un, nu, sn, ns, e); });
 }
 
 pt_effect* pt_effect_create_program(pt_ctx* c, int prog, const char* const* un, int nu, const char* const* sn, int ns,
                                     int* err)
 {
-    if (err) *err = PT_OK;
-    if (!c) { if (err) *err = PT_ERR_ARG; return nullptr; }
-    auto* fx = new pt_effect();
-    fx->ctx = c;
-    for (int k = 0; k < c->n(); k++) {
-        int rc = PT_OK;
-        DevFx* f = dev_effect_create_program(c->parts[k], prog, un, nu, sn, ns, &rc);
-        if (!f) {
-            take(c, k, rc);
-            for (auto* g : fx->sub) dev_effect_destroy(g);
-            delete fx;
-            if (err) *err = rc;
-            return nullptr;
-        }
-        fx->sub.push_back(f);
-    }
-    fx->prog = prog;
-    c->effects.insert(fx);
-    return fx;
+    return make_fx(c, err, [&](Dev* d, int* e) { return dev_effect_create_program(d, prog, un, nu, sn, ns, e); });
 }
 
 void pt_effect_destroy(pt_effect* fx)
@@ -433,25 +411,20 @@ int pt_effect_program(const pt_effect* fx) { return fx ? fx->prog : PT_PROG_UNKN
 int pt_set_float(pt_effect* fx, const char* name, const float* v, int n)
 {
     if (!fx) return PT_ERR_ARG;
-    for (size_t k = 0; k < fx->sub.size(); k++)
-        if (int rc = take(fx->ctx, (int)k, dev_set_float(fx->sub[k], name, v, n))) return rc;
-    return PT_OK;
+    return each(fx->ctx, [&](int k) { return dev_set_float(fx->sub[k], name, v, n); });
 }
 
 int pt_set_int(pt_effect* fx, const char* name, int v)
 {
     if (!fx) return PT_ERR_ARG;
-    for (size_t k = 0; k < fx->sub.size(); k++)
-        if (int rc = take(fx->ctx, (int)k, dev_set_int(fx->sub[k], name, v))) return rc;
-    return PT_OK;
+    return each(fx->ctx, [&](int k) { return dev_set_int(fx->sub[k], name, v); });
 }
 
 int pt_set_texture(pt_effect* fx, const char* name, pt_texture* t)
 {
     if (!fx || !name) return PT_ERR_ARG;
     if (t && t->ctx != fx->ctx) return fail(fx->ctx, PT_ERR_ARG, "texture belongs to another context");
-    for (size_t k = 0; k < fx->sub.size(); k++)
-        if (int rc = take(fx->ctx, (int)k, dev_set_texture(fx->sub[k], name, t ? t->sub[k] : nullptr))) return rc;
+    if (int rc = each(fx->ctx, [&](int k) { return dev_set_texture(fx->sub[k], name, t ? t->sub[k] : nullptr); })) return rc;
     fx->bound[name] = t;
     return PT_OK;
 }
@@ -459,21 +432,21 @@ int pt_set_texture(pt_effect* fx, const char* name, pt_texture* t)
 
 pt_texture* pt_texture_create_rgba32f(pt_ctx* c, int w, int h, const float* data, int sampling, int invert_y, int* err)
 {
-    return make_tex(c, K_F32, w, h, err, [&](Dev* d, int* e) {
+    return make_tex(c, TEX_F32, w, h, err, [&](Dev* d, int* e) {
         return dev_texture_create_rgba32f(d, w, h, data, sampling, invert_y, e);
     });
 }
 
 pt_texture* pt_texture_create_rgba8(pt_ctx* c, int w, int h, const uint8_t* data, int sampling, int invert_y, int* err)
 {
-    return make_tex(c, K_U8, w, h, err, [&](Dev* d, int* e) {
+    return make_tex(c, TEX_U8, w, h, err, [&](Dev* d, int* e) {
         return dev_texture_create_rgba8(d, w, h, data, sampling, invert_y, e);
     });
 }
 
 pt_texture* pt_render_target_create(pt_ctx* c, int w, int h, int* err)
 {
-    return make_tex(c, K_RT, w, h, err, [&](Dev* d, int* e) { return dev_render_target_create(d, w, h, e); });
+    return make_tex(c, TEX_RT, w, h, err, [&](Dev* d, int* e) { return dev_render_target_create(d, w, h, e); });
 }
 
 pt_texture* pt_render_target_wrap(pt_ctx* c, int w, int h, void* dptr, int* err)
@@ -483,7 +456,7 @@ pt_texture* pt_render_target_wrap(pt_ctx* c, int w, int h, void* dptr, int* err)
         if (err) *err = PT_ERR_ARG;
         return nullptr;
     }
-    return make_tex(c, K_RT, w, h, err, [&](Dev* d, int* e) { return dev_render_target_wrap(d, w, h, dptr, e); });
+    return make_tex(c, TEX_RT, w, h, err, [&](Dev* d, int* e) { return dev_render_target_wrap(d, w, h, dptr, e); });
 }
 
 int pt_render_target_resize(pt_texture* t, int w, int h)
@@ -491,8 +464,7 @@ int pt_render_target_resize(pt_texture* t, int w, int h)
     if (!t) return PT_ERR_ARG;
     if (t->ctx->n() > 1)   // neighbours' queued halo pulls / the gather may read this target's parts
         if (int rc = pt_sync(t->ctx)) return rc;
-    for (size_t k = 0; k < t->sub.size(); k++)
-        if (int rc = take(t->ctx, (int)k, dev_render_target_resize(t->sub[k], w, h))) return rc;
+    if (int rc = each(t->ctx, [&](int k) { return dev_render_target_resize(t->sub[k], w, h); })) return rc;
     t->w = w; t->h = h;
     return PT_OK;
 }
@@ -529,7 +501,7 @@ int pt_render(pt_effect* fx, pt_texture* target)
     const bool trace = is_trace(fx->prog);
     for (int k = 0; k < N; k++) {
         if (trace) {   // the neighbours' last output pulled halo rows from this part's targets
-            GHIP(c, hipSetDevice(dev_device(c->parts[k])));
+            HIPCHK(c, hipSetDevice(dev_device(c->parts[k])));
             const int lo = (k + N - 1) % N, hi = (k + 1) % N;
             if (int rc = wait(c, k, c->ev_out[lo], c->has_out[lo])) return rc;
             if (int rc = wait(c, k, c->ev_out[hi], c->has_out[hi])) return rc;
@@ -547,7 +519,7 @@ int pt_read_pixels(pt_ctx* c, const pt_texture* t, void* dst, size_t bytes)
 {
     if (!c || !dst) return PT_ERR_ARG;
     const int N = c->n();
-    if (N == 1 || !t || t->kind != K_RT) {
+    if (N == 1 || !t || t->kind != TEX_RT) {
         if (N > 1 && !t)   // the gathered canvas: every part's output first
             if (int rc = pt_sync(c)) return rc;
         return take(c, 0, dev_read_pixels(c->parts[0], t ? t->sub[0] : nullptr, dst, bytes));
@@ -555,12 +527,11 @@ int pt_read_pixels(pt_ctx* c, const pt_texture* t, void* dst, size_t bytes)
     // a render target is distributed by bands: each part's own bands
     const size_t need = (size_t)t->w * t->h * 16;
     if (bytes < need) return fail(c, PT_ERR_ARG, "destination too small");
-    const int nb = (t->h + kBand - 1) / kBand;
     for (int k = 0; k < N; k++) {
         Dev* d = c->parts[k];
         if (int rc = take(c, k, dev_flush(d))) return rc;
-        GHIP(c, copy_band_rows((char*)dst, (const char*)dev_texture_device_ptr(t->sub[k]), (size_t)t->w * 16, N, k,
-                               bands_of(nb, N, k), 0, kBand, t->h, hipMemcpyDeviceToHost, dev_stream(d)));
+        HIPCHK(c, copy_band_rows((char*)dst, (const char*)dev_texture_device_ptr(t->sub[k]), (size_t)t->w * 16, N, k,
+                                 pt::bands_owned(t->h, N, k), 0, pt::kTile, t->h, hipMemcpyDeviceToHost, dev_stream(d)));
     }
     return pt_sync(c);
 }
@@ -571,7 +542,7 @@ int pt_write_pixels(pt_ctx* c, pt_texture* t, const void* src, size_t bytes)
     const int N = c->n();
     for (int k = 0; k < N; k++) {
         if (N > 1) {   // after the neighbours' last output, whose halo pulls read this part's texels
-            GHIP(c, hipSetDevice(dev_device(c->parts[k])));
+            HIPCHK(c, hipSetDevice(dev_device(c->parts[k])));
             const int lo = (k + N - 1) % N, hi = (k + 1) % N;
             if (int rc = wait(c, k, c->ev_out[lo], c->has_out[lo])) return rc;
             if (int rc = wait(c, k, c->ev_out[hi], c->has_out[hi])) return rc;
@@ -584,17 +555,13 @@ int pt_write_pixels(pt_ctx* c, pt_texture* t, const void* src, size_t bytes)
 int pt_set_backend(pt_ctx* c, int backend)
 {
     if (!c) return PT_ERR_ARG;
-    for (int k = 0; k < c->n(); k++)
-        if (int rc = take(c, k, dev_set_backend(c->parts[k], backend))) return rc;
-    return PT_OK;
+    return each(c, [&](int k) { return dev_set_backend(c->parts[k], backend); });
 }
 
 int pt_set_bvh_layout(pt_ctx* c, int layout)
 {
     if (!c) return PT_ERR_ARG;
-    for (int k = 0; k < c->n(); k++)
-        if (int rc = take(c, k, dev_set_bvh_layout(c->parts[k], layout))) return rc;
-    return PT_OK;
+    return each(c, [&](int k) { return dev_set_bvh_layout(c->parts[k], layout); });
 }
 
 int pt_bvh_layout_used(pt_ctx* c) { return c ? dev_bvh_layout_used(c->parts[0]) : PT_ERR_ARG; }
@@ -623,9 +590,7 @@ int pt_last_render_ms(pt_ctx* c, int prog, float* ms)
 int pt_timing_begin(pt_ctx* c)
 {
     if (!c) return PT_ERR_ARG;
-    for (int k = 0; k < c->n(); k++)
-        if (int rc = take(c, k, dev_timing_begin(c->parts[k]))) return rc;
-    return PT_OK;
+    return each(c, [&](int k) { return dev_timing_begin(c->parts[k]); });
 }
 
 int pt_timing_end(pt_ctx* c, int prog, double* total_ms, int* launches)
@@ -663,54 +628,31 @@ int pt_timing_latency(pt_ctx* c, int prog, float* ms, int cap, int* n)
 int pt_set_counting(pt_ctx* c, int enable)
 {
     if (!c) return PT_ERR_ARG;
-    for (int k = 0; k < c->n(); k++)
-        if (int rc = take(c, k, dev_set_counting(c->parts[k], enable))) return rc;
-    return PT_OK;
+    return each(c, [&](int k) { return dev_set_counting(c->parts[k], enable); });
 }
 
 int pt_read_counters(pt_ctx* c, uint64_t out[PT_NUM_COUNTERS])
 {
     if (!c || !out) return PT_ERR_ARG;
-    std::memset(out, 0, PT_NUM_COUNTERS * sizeof(uint64_t));
-    for (int k = 0; k < c->n(); k++) {
-        uint64_t v[PT_NUM_COUNTERS];
-        if (int rc = take(c, k, dev_read_counters(c->parts[k], v))) return rc;
-        for (int i = 0; i < PT_NUM_COUNTERS; i++) out[i] += v[i];
-    }
-    return PT_OK;
+    return sum_parts<PT_NUM_COUNTERS>(c, out, dev_read_counters);
 }
 
 int pt_reset_counters(pt_ctx* c)
 {
     if (!c) return PT_ERR_ARG;
-    for (int k = 0; k < c->n(); k++)
-        if (int rc = take(c, k, dev_reset_counters(c->parts[k]))) return rc;
-    return PT_OK;
+    return each(c, [&](int k) { return dev_reset_counters(c->parts[k]); });
 }
 
 int pt_queue_stats(pt_ctx* c, uint32_t out[16])
 {
     if (!c || !out) return PT_ERR_ARG;
-    std::memset(out, 0, 16 * sizeof(uint32_t));
-    for (int k = 0; k < c->n(); k++) {
-        uint32_t v[16];
-        if (int rc = take(c, k, dev_queue_stats(c->parts[k], v))) return rc;
-        for (int i = 0; i < 16; i++) out[i] += v[i];
-    }
-    return PT_OK;
+    return sum_parts<16>(c, out, dev_queue_stats);
 }
 
 int pt_cont_stats(pt_ctx* c, uint64_t out[2])
 {
     if (!c || !out) return PT_ERR_ARG;
-    out[0] = out[1] = 0;
-    for (int k = 0; k < c->n(); k++) {
-        uint64_t v[2];
-        if (int rc = take(c, k, dev_cont_stats(c->parts[k], v))) return rc;
-        out[0] += v[0];
-        out[1] += v[1];
-    }
-    return PT_OK;
+    return sum_parts<2>(c, out, dev_cont_stats);
 }
 
 int pt_set_feature_targets(pt_effect* fx, pt_texture* normal_id, pt_texture* albedo_weight)
@@ -719,14 +661,13 @@ int pt_set_feature_targets(pt_effect* fx, pt_texture* normal_id, pt_texture* alb
     pt_ctx* c = fx->ctx;
     if (!is_trace(fx->prog)) return fail(c, PT_ERR_ARG, "feature targets need a path-tracing effect");
     for (pt_texture* t : { normal_id, albedo_weight })
-        if (t && (t->ctx != c || t->kind != K_RT))
+        if (t && (t->ctx != c || t->kind != TEX_RT))
             return fail(c, PT_ERR_ARG, "a feature target must be a render target of this context");
     // every part folds its own bands into its share of the targets (distributed by bands like any render target)
-    for (size_t k = 0; k < fx->sub.size(); k++)
-        if (int rc = take(c, (int)k, dev_set_feature_targets(fx->sub[k], normal_id ? normal_id->sub[k] : nullptr,
-                                                             albedo_weight ? albedo_weight->sub[k] : nullptr)))
-            return rc;
-    return PT_OK;
+    return each(c, [&](int k) {
+        return dev_set_feature_targets(fx->sub[k], normal_id ? normal_id->sub[k] : nullptr,
+                                       albedo_weight ? albedo_weight->sub[k] : nullptr);
+    });
 }
 
 int pt_math_probe(pt_ctx* c, int op, const float* x, const float* y, float* out, int n)

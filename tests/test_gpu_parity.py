@@ -759,6 +759,60 @@ def test_malformed_bvh_links_fall_back_exactly(engine, backend_name):
         assert _bits_equal(ra, ga), _diff_report(ra, ga)
 
 
+@pytest.mark.parametrize("layout", ["pairs", "trail"])
+def test_child_pair_tree_follows_the_triangle_texture(engine, layout):
+    """The child-pair records are cached on the BVH texture and hold the triangles' vertices: they must be rebuilt
+    when the triangle texture drawn with it is another one (a destroyed texture's tree is invalid even if the next
+    one lands at its address) and when its texels are rewritten in place (the generation), with the BVH texture
+    untouched both times. A stale tree would still render a plausible teapot."""
+    import babylon_pt as bp
+    meta = H.stream("gltf_teapot_320x180")
+    mesh = H.mesh(meta)
+    # every triangle's vertices moved halfway to its centroid: every BVH box still bounds its triangle
+    pos = mesh["tri"][:, 0:9].astype(np.float64).reshape(-1, 3, 3)
+    tri2 = mesh["tri"].copy()
+    tri2[:, 0:9] = ((pos + pos.mean(1, keepdims=True)) * 0.5).reshape(-1, 9).astype(np.float32)
+    small = dict(mesh, tri=tri2)
+    ref1, _, _ = H.oracle_replay(meta, 2)
+    ref2, _, _ = H.oracle_replay(meta, 2, mesh=small)
+    raw_bvh, raw_tri = (next(raw for raw, kind in meta["textures"].items() if kind == k) for k in ("bvh", "tri"))
+    engine.set_bvh_layout(layout)
+    try:
+        player = bp.StreamPlayer(engine, meta, H.bluenoise(), H.texture_payloads(meta, mesh))
+        bvh_handle = player.textures[raw_bvh].handle
+
+        def two_frames():
+            zero = np.zeros((player.height, player.width, 4), np.float32)
+            for name in ("pathTracingRenderTarget", "screenCopyRenderTarget"):
+                player.textures[name].write(zero)
+            got = []
+            for i in range(2):
+                player.play_frame(i)
+                engine.sync()
+                got.append(player.textures["pathTracingRenderTarget"].read())
+            assert engine.bvh_layout_used() == layout
+            return got
+
+        first = two_frames()
+        # another triangle texture in its place
+        player.textures[raw_tri].dispose()
+        player.textures[raw_tri] = bp.RawTexture.CreateRGBATexture(H.texture_payloads(meta, small)["tri"], 2048, 2048, engine,
+                                                                  name="tri")
+        second = two_frames()
+        # ... and its texels rewritten in place, through the texture's handle
+        back = np.ascontiguousarray(H.texture_payloads(meta, mesh)["tri"], dtype=np.float32)
+        engine.check(bp.lib().pt_write_pixels(engine.ctx, player.textures[raw_tri].handle, back.ctypes.data, back.nbytes), "write")
+        third = two_frames()
+        assert player.textures[raw_bvh].handle == bvh_handle
+    finally:
+        engine.set_bvh_layout("pairs")
+    for i in range(2):
+        assert _bits_equal(ref1[i], first[i]), "first pass, frame %d: %s" % (i, _diff_report(ref1[i], first[i]))
+        assert _bits_equal(ref2[i], second[i]), "other triangle texture, frame %d: %s" % (i, _diff_report(ref2[i], second[i]))
+        assert _bits_equal(ref1[i], third[i]), "texels rewritten in place, frame %d: %s" % (i, _diff_report(ref1[i], third[i]))
+    assert any(not _bits_equal(a, b) for a, b in zip(first, second)), "the moved vertices change no pixel"
+
+
 def test_errors_are_codes_not_crashes(engine):
     import babylon_pt as bp
     with pytest.raises(bp.PtError, match="PT_ERR_SHADER"):

@@ -1,8 +1,10 @@
-"""The draw schedule's arithmetic (csrc/pt_plan.h): bands and pixels of a partition, the compaction slab's layout,
-the overlap's buffer set / stream / mark, the megakernel's grid and the auto trial of late-bounce compaction.
-Host C++ only: a small program over the header, no GPU. Every expectation is a literal worked out by hand from
-the host code as it stood before the header existed (pt_capi.cpp's render_trace, cont_decide, cont_bytes), not
-produced by the header."""
+"""The draw schedule's arithmetic (csrc/pt_plan.h): bands and pixels of a partition, the carved slabs' layouts
+(compaction records, the child-pair build's scratch and records, the wavefront buffers, the longest-first arrays,
+the spill slabs), the overlap's buffer set / stream / mark, the megakernel's grid and the auto trial of late-bounce
+compaction. Host C++ only: a small program over the header, no GPU. Every expectation is a literal worked out by
+hand from the host code as it stood before the arithmetic moved into the header (pt_capi.cpp's render_trace,
+cont_decide, cont_bytes; ensure_pairs, wf_reserve, lpt_cost / lpt_order / lpt_split, spill_reserve), not produced
+by the header."""
 import os
 import shutil
 import subprocess
@@ -36,6 +38,28 @@ int main(int argc, char** argv)
         const pt::ContLayout L((size_t)num(argv[2]), num(argv[3]) != 0);
         std::printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %d %d %d", L.bytes, L.rec, L.aux, L.perm, L.rank, L.key, L.bins, L.count,
                     L.total(), (int)pt::ContLayout::kStored, (int)pt::ContLayout::kHead, (int)pt::ContLayout::kTotal);
+    } else if (!std::strcmp(cmd, "pairs")) {   // pairs texels n_inner n_leaf
+        const pt::PairsLayout L((long long)num(argv[2]));
+        const pt::PairsLayout::Records R((size_t)num(argv[3]), (size_t)num(argv[4]));
+        std::printf("%u %u %zu %zu %zu %zu %zu %zu %zu %u %zu %zu %zu", L.nrec, L.nblk, L.inner, L.leafref, L.counts, L.code,
+                    L.parent, L.refs, L.bytes, R.leaf_base, R.top_base, R.rec_bytes, R.alloc);
+    } else if (!std::strcmp(cmd, "wf")) {      // wf tiles pixels blocks
+        const unsigned cap = pt::WfLayout::shard_cap((int)num(argv[2]));
+        const size_t slots = (size_t)cap * pt::kShards, spill = pt::WfLayout::spill_entries((int)num(argv[4]));
+        const pt::WfLayout L(slots, (size_t)num(argv[3]), spill);
+        std::printf("%u %zu %zu %zu %zu ", cap, slots, spill, L.end, L.bytes);
+        std::printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu ", L.cnt, L.q[0][0], L.q[0][1], L.q[0][2], L.q[0][3], L.q[1][0], L.q[1][1],
+                    L.q[1][2], L.q[1][3]);
+        std::printf("%zu %zu %zu %zu %zu %zu %zu", L.hit[0], L.hit[1], L.gb[0], L.gb[1], L.rad, L.bvhq, L.spill);
+    } else if (!std::strcmp(cmd, "lpt")) {     // lpt cap set
+        const pt::LptLayout L{ (size_t)num(argv[2]) };
+        const int p = (int)num(argv[3]);
+        std::printf("%zu %zu %zu %zu %d", L.cost(p), L.order(p), L.split(p), L.words(), pt::kSetsMax);
+    } else if (!std::strcmp(cmd, "spill")) {   // spill p lanes...
+        std::printf("%zu ", pt::kSpillPerLane);
+        for (int i = 3; i < argc; i++)
+            std::printf("%d %zu ", (int)pt::spill_fits((size_t)std::strtoull(argv[i], nullptr, 10)),
+                        pt::spill_slab((int)num(argv[2]), (size_t)std::strtoull(argv[i], nullptr, 10)));
     } else if (!std::strcmp(cmd, "overlap")) { // overlap depth,lag,overlapped[,f: memory grew before this draw] ...
         pt::Overlap o;
         for (int i = 2; i < argc; i++) {
@@ -199,6 +223,90 @@ def test_cont_layout(plan):
     got = dict(zip(names, plan("layout", 100, 1)))
     assert (got["aux"], got["perm"], got["rank"], got["key"], got["bins"], got["count"], got["bytes"]) == \
         (6400, 6912, 7424, 7936, 8192, 40960, 41216)
+
+
+# ---- the other carved slabs. Each array starts where the one before it ends, rounded up to 256 B; none overlap
+def check_carve(starts, sizes, end):
+    """starts / sizes in carving order: array k + 1 starts at the end of array k rounded up to 256, the last ends at `end`"""
+    assert len(starts) == len(sizes)
+    for k, (at, size) in enumerate(zip(starts, sizes)):
+        assert at % 256 == 0
+        nxt = starts[k + 1] if k + 1 < len(starts) else end
+        assert nxt == at + (size + 255) // 256 * 256, k      # (so no two overlap: every size is at most its rounding)
+
+
+PAIRS = ("nrec", "nblk", "inner", "leafref", "counts", "code", "parent", "refs", "bytes", "leaf_base", "top_base", "rec_bytes", "alloc")
+
+
+def test_pairs_layout_smallest(plan):
+    # 2 texels: one node, one scan block; ensure_pairs: 2 al(1) + al(2 * 1 * 4) + al(1 * 4) + 2 al(1 * 4) = 6 x 256
+    g = dict(zip(PAIRS, plan("pairs", 2, 0, 1)))
+    assert (g["nrec"], g["nblk"]) == (1, 1)
+    assert [g[k] for k in PAIRS[2:9]] == [0, 256, 512, 768, 1024, 1280, 1536]
+    check_carve([g[k] for k in PAIRS[2:8]], [1, 1, 8, 4, 4, 4], g["bytes"])
+    # no inner record: the one leaf record at byte 0, the jump table (4095 x 64 B) after its 48 B rounded up
+    assert (g["leaf_base"], g["top_base"], g["rec_bytes"], g["alloc"]) == (0, 256, 256 + 262080, 256 + 262080 + 256)
+    assert dict(zip(PAIRS, plan("pairs", 1, 0, 1)))["nrec"] == 1   # an odd texel count rounds up: (1 + 1) / 2
+
+
+def test_pairs_layout_across_a_block_and_every_rounding(plan):
+    # 2999 texels -> nrec 1500, two 1024-node blocks: flags 1500 -> 1536 B each, counts 16 -> 256 B, words 6000 -> 6144 B
+    g = dict(zip(PAIRS, plan("pairs", 2999, 749, 750)))
+    assert (g["nrec"], g["nblk"]) == (1500, 2)
+    assert [g[k] for k in PAIRS[2:9]] == [0, 1536, 3072, 3328, 9472, 15616, 21760]
+    check_carve([g[k] for k in PAIRS[2:8]], [1500, 1500, 16, 6000, 6000, 6000], g["bytes"])
+    # 749 x 64 = 47936 -> 48128; 750 x 48 = 36000 -> 36096; + 4095 x 64 = 262080
+    assert (g["leaf_base"], g["top_base"], g["rec_bytes"], g["alloc"]) == (48128, 84224, 346304, 346560)
+    assert dict(zip(PAIRS, plan("pairs", 2048, 0, 1)))["nblk"] == 1 and dict(zip(PAIRS, plan("pairs", 2050, 0, 1)))["nblk"] == 2
+    g = dict(zip(PAIRS, plan("pairs", 1 << 24, 1, 1)))                # the largest tree the host builds
+    assert (g["nrec"], g["nblk"], g["bytes"]) == (1 << 23, 8192, 2 * (1 << 23) + 65536 + 3 * (1 << 25))
+
+
+WF = ("cap", "slots", "spill_n", "end", "bytes", "cnt", "qA0", "qB0", "qC0", "qD0", "qA1", "qB1", "qC1", "qD1", "hit0", "hit1",
+      "gb0", "gb1", "rad", "bvhq", "spill")
+
+
+def wf_sizes(g, pixels):
+    return [4096] + [g["slots"] * 16] * 10 + [pixels * 16] * 3 + [g["slots"] * 4, g["spill_n"] * 8]
+
+
+def test_wf_layout_one_tile(plan):
+    # one tile: a 256-slot shard x 16 shards; a 16 x 16 frame; 16 blocks: (28 - 7) x 16 x 256 stack entries
+    g = dict(zip(WF, plan("wf", 1, 256, 16)))
+    assert (g["cap"], g["slots"], g["spill_n"]) == (256, 4096, 86016)
+    assert [g[k] for k in WF[5:]] == [0] + [4096 + 65536 * k for k in range(10)] + [659456, 663552, 667648, 671744, 688128]
+    check_carve([g[k] for k in WF[5:]], wf_sizes(g, 256), g["end"])
+    # wf_reserve: 4096 + 10 x 65536 + 3 x 4096 + 16384 + 688128 + 16 x 256; every size here is a multiple of 256
+    assert g["bytes"] == 1380352 and g["end"] == 1376256 == g["bytes"] - 4096
+
+
+def test_wf_layout_tiles_no_multiple_of_the_shards(plan):
+    # 17 tiles: two tiles in shard 0, so 512 slots per shard; a 66 x 50 frame: 52800 B per plane -> 52992
+    g = dict(zip(WF, plan("wf", 17, 3300, 16)))
+    assert (g["cap"], g["slots"], g["spill_n"]) == (512, 8192, 86016)
+    assert [g[k] for k in WF[5:]] == [0] + [4096 + 131072 * k for k in range(10)] + [1314816, 1367808, 1420800, 1473792, 1506560]
+    check_carve([g[k] for k in WF[5:]], wf_sizes(g, 3300), g["end"])
+    assert g["end"] == 2194688 and g["bytes"] == 2198208             # allocated: 256 B of slack for each of 16 arrays
+    assert g["end"] <= g["bytes"]
+    assert dict(zip(WF, plan("wf", 16, 256, 16)))["cap"] == 256 and dict(zip(WF, plan("wf", 32, 256, 16)))["cap"] == 512
+
+
+def test_lpt_layout(plan):
+    # 100 tiles, 12 buffer sets: cost 12 x 400 words | order 12 x 100 | split 12
+    assert plan("lpt", 100, 0) == [0, 4800, 6000, 6012, 12]
+    assert plan("lpt", 100, 11) == [4400, 5900, 6011, 6012, 12]       # the last set: its split is the last word
+    assert plan("lpt", 100, 1)[:3] == [400, 4900, 6001]               # set 1 starts where set 0's 4 x cap / cap / 1 end
+    assert plan("lpt", 8160, 11) == [359040, 481440, 489611, 489612, 12]
+
+
+def test_spill_slab(plan):
+    # 28 - 6 stack levels + 4 entries of G-buffer fields = 26 entries per lane; 2^32 / 26 = 165191049.8
+    got = plan("spill", 2, 165191049, 165191050, 2088960)
+    assert got[0] == 26
+    assert got[1:3] == [1, 2 * 165191049 * 26] and 165191049 * 26 == 2 ** 32 - 22    # fits: the last index is below 2^32
+    assert got[3:5] == [0, 2 * 165191050 * 26] and 165191050 * 26 == 2 ** 32 + 4     # does not
+    assert got[5:7] == [1, 2 * 2088960 * 26]                                          # 120 x 68 tiles x 256 lanes, slab 2
+    assert plan("spill", 0, 1000)[1:] == [1, 0]
 
 
 GRID = ("n", "split_cap", "split", "gy_grid", "lanes", "one_wave", "order_zig", "cont_waves", "sort_bits")
