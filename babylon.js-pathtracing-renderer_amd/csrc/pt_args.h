@@ -273,4 +273,21 @@ struct CopyArgs {
     float4* dst;
 };
 
+// pt_denoise (pt_denoise.hip): the edge-avoiding à-trous filter over the feature buffers, whole frame. The host
+// carves three float4 planes of width * height out of one slab: colour[2] = {d.xyz, id}, the passes' ping-pong,
+// and guide = {n.xyz, valid}, which no pass changes.
+struct DenoiseArgs {
+    int width, height;
+    int iterations;         // 1..5: pass i taps at spacing 2^i
+    int demodulate;         // 0 | 1
+    float inv_n;            // 1 / sigma_normal^2
+    float inv_c0;           // 1 / sigma_colour^2 (pass i: x 4^i)
+    const float4* beauty;
+    const float4* normal_id;
+    const float4* albedo_weight;
+    float4* dst;
+    float4* colour[2];
+    float4* guide;
+};
+
 } // namespace pt

@@ -21,6 +21,7 @@
 //   SCREEN_COPY     -> pt_copy over the owned bands, deferred to fuse with the next screenOutput;
 //   SCREEN_OUTPUT   -> pt_output into the canvas (RGBA8) or an RGBA32F target, with a deferred copy
 //                      and order build riding along.
+// dev_denoise (pt_denoise) is no draw: the à-trous filter's prep and passes (pt_denoise.hip) on the main stream.
 // The main stream is the context's own or the caller's (dev_set_stream); per-draw timing events are off
 // until asked for (pt_last_render_ms, the timing window).
 #include "../../include/pt.h"
@@ -54,6 +55,7 @@ hipError_t pt_launch_feature_fold(const pt::FoldArgs* a, int bands, hipStream_t 
 hipError_t pt_launch_cont_sort(const pt::SortArgs* a, size_t cap, hipStream_t s);
 hipError_t pt_launch_cont(int prog, const pt::TraceArgs* a, int waves, hipStream_t s);
 hipError_t pt_launch_output(const pt::OutputArgs* a, hipStream_t s, int waves);
+hipError_t pt_launch_denoise(const pt::DenoiseArgs* a, hipStream_t s);
 hipError_t pt_launch_math_probe(int op, const float* x, const float* y, float* out, int n, hipStream_t s);
 hipError_t pt_launch_persist(int prog, int count, const pt::TraceArgs* a, const pt::WfBufs* w, int tiles_x,
                              unsigned n_wave_tiles, unsigned per_wave, unsigned refill, hipStream_t s);
@@ -133,8 +135,9 @@ struct Dev {
     // pt::LptLayout), SPILL the megakernel's BVH stack spill slabs, one per side stream of the overlap depth (lanes;
     // pt::spill_slab), RAD rad[sets()], radiance + flag (pixels), FEAT feat[sets()][2], the G-buffer pt_trace stages
     // for pt_feature_fold, once a draw has feature targets bound (pixels), CONT pt_cont's records (records per
-    // buffer set; pt::ContLayout), GB the persistent backend's G-buffer + radiance (pixels)
-    enum Slab { WF, LPT, SPILL, RAD, FEAT, CONT, GB, kSlabs };
+    // buffer set; pt::ContLayout), GB the persistent backend's G-buffer + radiance (pixels), DENOISE pt_denoise's
+    // three planes, colour[2] + guide (pixels)
+    enum Slab { WF, LPT, SPILL, RAD, FEAT, CONT, GB, DENOISE, kSlabs };
     DevMem slab[kSlabs];
     pt::WfBufs wf = {};
     size_t wf_pixels = 0, wf_spill = 0;
@@ -1548,6 +1551,47 @@ int dev_set_feature_targets(DevFx* fx, DevTex* normal_id, DevTex* albedo_weight)
             return fail(c, PT_ERR_ARG, "a feature target must be a render target of this context");
     fx->feat[0] = normal_id;
     fx->feat[1] = albedo_weight;
+    return PT_OK;
+}
+
+// pt_denoise: checked here, then prep and the passes on the main stream, where every draw's blend and feature fold
+// are (the side streams' path tracing reads and writes none of the four textures); no timing events, no counters
+int dev_denoise(Dev* c, const DevTex* beauty, const DevTex* normal_id, const DevTex* albedo_weight, DevTex* dst,
+                int iterations, float sigma_normal, float sigma_colour, int demodulate)
+{
+    if (!c) return PT_ERR_ARG;
+    const DevTex* const in[3] = { beauty, normal_id, albedo_weight };
+    if (!dst || dst->ctx != c || dst->kind != TEX_RT) return fail(c, PT_ERR_ARG, "pt_denoise: dst must be a render target of this context");
+    for (const DevTex* t : in) {
+        if (!t || t->ctx != c || t->kind != TEX_RT) return fail(c, PT_ERR_ARG, "pt_denoise: the inputs must be render targets of this context");
+        if (t->w != dst->w || t->h != dst->h) return fail(c, PT_ERR_ARG, "pt_denoise: the four textures must have one size");
+        if (t == dst || t->d == dst->d) return fail(c, PT_ERR_ARG, "pt_denoise: dst must not be an input");
+    }
+    if (iterations < 1 || iterations > 5) return fail(c, PT_ERR_ARG, "pt_denoise: iterations must be 1..5");
+    if (!(std::isfinite(sigma_normal) && sigma_normal > 0.0f && std::isfinite(sigma_colour) && sigma_colour > 0.0f))
+        return fail(c, PT_ERR_ARG, "pt_denoise: the sigmas must be finite and > 0");
+    if (demodulate != 0 && demodulate != 1) return fail(c, PT_ERR_ARG, "pt_denoise: demodulate must be 0 or 1");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = flush_copy(c)) return rc;
+    const size_t pixels = (size_t)dst->w * dst->h;
+    DevMem& mem = c->slab[Dev::DENOISE];
+    if (pixels > mem.size)
+        if (int rc = mem.grow(c, pixels, 3 * pixels * sizeof(float4), WAIT_MAIN, false)) return rc;
+    pt::DenoiseArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.width = dst->w; a.height = dst->h;
+    a.iterations = iterations;
+    a.demodulate = demodulate;
+    a.inv_n = 1.0f / (sigma_normal * sigma_normal);
+    a.inv_c0 = 1.0f / (sigma_colour * sigma_colour);
+    a.beauty = (const float4*)beauty->d;
+    a.normal_id = (const float4*)normal_id->d;
+    a.albedo_weight = (const float4*)albedo_weight->d;
+    a.dst = (float4*)dst->d;
+    a.colour[0] = mem.as<float4>();
+    a.colour[1] = a.colour[0] + mem.size;
+    a.guide = a.colour[1] + mem.size;
+    HIPCHK(c, pt_launch_denoise(&a, c->stream));
     return PT_OK;
 }
 

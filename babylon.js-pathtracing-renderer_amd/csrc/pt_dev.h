@@ -65,6 +65,8 @@ int dev_timing_latency(Dev* c, int prog, float* ms, int cap, int* n);
 int dev_queue_stats(Dev* c, uint32_t out[16]);
 int dev_cont_stats(Dev* c, uint64_t out[2]);
 int dev_set_feature_targets(DevFx* fx, DevTex* normal_id, DevTex* albedo_weight);
+int dev_denoise(Dev* c, const DevTex* beauty, const DevTex* normal_id, const DevTex* albedo_weight, DevTex* dst,
+                int iterations, float sigma_normal, float sigma_colour, int demodulate);
 int dev_math_exhaustive(Dev* c, int op, uint64_t* mismatches);
 int dev_math_probe(Dev* c, int op, const float* x, const float* y, float* out, int n);
 

@@ -670,6 +670,19 @@ int pt_set_feature_targets(pt_effect* fx, pt_texture* normal_id, pt_texture* alb
     });
 }
 
+int pt_denoise(pt_ctx* c, const pt_texture* beauty, const pt_texture* normal_id, const pt_texture* albedo_weight,
+               pt_texture* dst, int iterations, float sigma_normal, float sigma_colour, int demodulate)
+{
+    if (!c) return PT_ERR_ARG;
+    for (const pt_texture* t : { beauty, normal_id, albedo_weight, (const pt_texture*)dst })
+        if (!t || t->ctx != c || t->kind != TEX_RT)
+            return fail(c, PT_ERR_ARG, "pt_denoise takes four render targets of this context");
+    // (a part's targets hold its own bands only, and the taps reach +-32 rows)
+    if (c->n() > 1) return fail(c, PT_ERR_UNSUPPORTED, "pt_denoise needs a one-part context");
+    return take(c, 0, dev_denoise(c->parts[0], beauty->sub[0], normal_id->sub[0], albedo_weight->sub[0], dst->sub[0],
+                                  iterations, sigma_normal, sigma_colour, demodulate));
+}
+
 int pt_math_probe(pt_ctx* c, int op, const float* x, const float* y, float* out, int n)
 {
     if (!c) return PT_ERR_ARG;

@@ -20,6 +20,7 @@
 //   effect.setFloat/.../setMatrix/setTexture      -> pt_set_float / pt_set_int / pt_set_texture (:813-848)
 //   new BABYLON.EffectRenderer(engine).render()   -> pt_render (:1230-1235)
 //   effect.setFeatureTargets(normalRT, albedoRT)  -> pt_set_feature_targets (extension: accumulated G-buffer)
+//   engine.denoise(beautyRT, normalRT, albedoRT, dstRT, opts) -> pt_denoise (extension: a-trous filter over them)
 'use strict';
 const fs = require('fs');
 const path = require('path');
@@ -185,6 +186,17 @@ function install(BABYLON, opts) {
       const out = new Uint8Array(this.getRenderWidth() * this.getRenderHeight() * 4);
       check(this._pt, addon.pt_read_pixels(this._pt, null, out), 'readPixels');
       return out;
+    }
+    // MI355X extension (pt_denoise): the edge-avoiding a-trous filter of the RenderTargetTexture `beauty`, guided
+    // by the feature targets accumulated beside it (effect.setFeatureTargets), into `dst`: the accumulation's
+    // scale, sharpness flags 1, so screenOutput with `dst` as its accumulationBuffer tone-maps it unchanged.
+    // o: { iterations = 3, sigmaNormal = 0.5, sigmaColour = 1.0, demodulate = true }. Asynchronous.
+    denoise(beauty, normalRT, albedoRT, dst, o) {
+      o = o || {};
+      const pt = (t) => (t ? t._pt : null);
+      return check(this._pt, addon.pt_denoise(this._pt, pt(beauty), pt(normalRT), pt(albedoRT), pt(dst),
+        o.iterations === undefined ? 3 : o.iterations | 0, o.sigmaNormal === undefined ? 0.5 : +o.sigmaNormal,
+        o.sigmaColour === undefined ? 1.0 : +o.sigmaColour, o.demodulate === undefined || o.demodulate ? 1 : 0), 'denoise');
     }
     dispose() { if (this._pt) { addon.pt_ctx_destroy(this._pt); this._pt = null; } super.dispose(); }
   }

@@ -16,7 +16,7 @@
 
 #include "pt.h"
 
-#define MAXARGS 8
+#define MAXARGS 9
 #define CHECK(call) do { if ((call) != napi_ok) { napi_throw_error(env, NULL, #call " failed"); return NULL; } } while (0)
 
 static napi_value num(napi_env env, double v) { napi_value r; napi_create_double(env, v, &r); return r; }
@@ -380,6 +380,15 @@ static napi_value SetFeatureTargets(napi_env env, napi_callback_info info)
     return num(env, pt_set_feature_targets((pt_effect*)handle(env, a[0]), (pt_texture*)handle(env, a[1]),
                                            (pt_texture*)handle(env, a[2])));
 }
+/* pt_denoise(ctx, beauty, normalId, albedoWeight, dst, iterations, sigmaNormal, sigmaColour, demodulate) -> status */
+static napi_value Denoise(napi_env env, napi_callback_info info)
+{
+    napi_value a[MAXARGS]; if (args(env, info, a, 9) < 0) return NULL;
+    return num(env, pt_denoise((pt_ctx*)handle(env, a[0]), (const pt_texture*)handle(env, a[1]),
+                               (const pt_texture*)handle(env, a[2]), (const pt_texture*)handle(env, a[3]),
+                               (pt_texture*)handle(env, a[4]), i32(env, a[5]), (float)f64(env, a[6]),
+                               (float)f64(env, a[7]), i32(env, a[8])));
+}
 /* pt_bvh_build(aabbIn: Float32Array (9 per triangle), work: Uint32Array, out: Float32Array) -> node count */
 static napi_value BvhBuild(napi_env env, napi_callback_info info)
 {
@@ -456,7 +465,7 @@ static napi_value Init(napi_env env, napi_value exports)
         { "pt_last_render_ms", LastRenderMs }, { "pt_timing_begin", TimingBegin }, { "pt_timing_end", TimingEnd },
         { "pt_timing_latency", TimingLatency },
         { "pt_set_counting", SetCounting }, { "pt_read_counters", ReadCounters }, { "pt_reset_counters", ResetCounters }, { "pt_queue_stats", QueueStats }, { "pt_cont_stats", ContStats },
-        { "pt_set_feature_targets", SetFeatureTargets },
+        { "pt_set_feature_targets", SetFeatureTargets }, { "pt_denoise", Denoise },
         { "pt_bvh_build", BvhBuild }, { "pt_bvh_build_gpu", BvhBuildGpu },
         { "pt_jpeg_size", JpegSize }, { "pt_jpeg_decode_rgba8", JpegDecode }, { "pt_version", Version },
     };

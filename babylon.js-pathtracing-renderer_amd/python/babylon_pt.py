@@ -40,7 +40,7 @@ SYMBOLS = [
     "pt_render_target_resize", "pt_texture_size", "pt_texture_destroy",
     "pt_render", "pt_read_pixels", "pt_write_pixels",
     "pt_set_row_partition", "pt_set_output_partition", "pt_canvas_wrap", "pt_set_backend", "pt_set_bvh_layout", "pt_bvh_layout_used", "pt_set_stream", "pt_texture_device_ptr", "pt_last_render_ms", "pt_timing_begin", "pt_timing_end", "pt_timing_latency",
-    "pt_set_counting", "pt_read_counters", "pt_reset_counters", "pt_queue_stats", "pt_cont_stats", "pt_set_feature_targets", "pt_math_probe", "pt_math_exhaustive", "pt_bvh_build", "pt_bvh_build_gpu", "pt_jpeg_size", "pt_jpeg_decode_rgba8", "pt_version",
+    "pt_set_counting", "pt_read_counters", "pt_reset_counters", "pt_queue_stats", "pt_cont_stats", "pt_set_feature_targets", "pt_denoise", "pt_math_probe", "pt_math_exhaustive", "pt_bvh_build", "pt_bvh_build_gpu", "pt_jpeg_size", "pt_jpeg_decode_rgba8", "pt_version",
 ]
 
 _lib = None
@@ -91,6 +91,7 @@ def lib():
         "pt_math_exhaustive": ([vp, i32, vp], i32),
         "pt_cont_stats": ([vp, ctypes.POINTER(ctypes.c_uint64)], i32),
         "pt_set_feature_targets": ([vp, vp, vp], i32),
+        "pt_denoise": ([vp, vp, vp, vp, vp, i32, ctypes.c_float, ctypes.c_float, i32], i32),
         "pt_queue_stats": ([vp, ctypes.POINTER(ctypes.c_uint32)], i32), "pt_version": ([], ctypes.c_char_p),
     }
     for name, (args, res) in sig.items():
@@ -241,6 +242,15 @@ class Engine:
         buf = (ctypes.c_uint64 * 2)()
         self.check(lib().pt_cont_stats(self.ctx, buf), "pt_cont_stats")
         return int(buf[0]), int(buf[1])
+
+    def denoise(self, beauty, normal_id, albedo_weight, dst, iterations=3, sigma_normal=0.5, sigma_colour=1.0,
+                demodulate=True):
+        """MI355X extension (pt_denoise): the edge-avoiding a-trous filter of the render target `beauty`, guided by
+        the feature targets accumulated beside it (Effect.set_feature_targets), into the render target `dst`, in
+        the accumulation's scale with every sharpness flag 1: screenOutput with `dst` as its accumulationBuffer
+        tone-maps it unchanged. Asynchronous, on the engine's stream after everything queued so far."""
+        self.check(lib().pt_denoise(self.ctx, beauty.handle, normal_id.handle, albedo_weight.handle, dst.handle,
+                                    int(iterations), float(sigma_normal), float(sigma_colour), int(demodulate)), "pt_denoise")
 
     def math_probe(self, op, x, y=None):
         x = np.ascontiguousarray(x, dtype=np.float32)

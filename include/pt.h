@@ -255,6 +255,28 @@ int pt_cont_stats(pt_ctx* ctx, uint64_t out[2]);
  * when it is the draw target, the bound previousBuffer or the other feature target. Destroying a bound
  * texture unbinds it. */
 int pt_set_feature_targets(pt_effect* fx, pt_texture* normal_id, pt_texture* albedo_weight);
+/* Denoising: the edge-avoiding a-trous filter (5x5 B3-spline taps at spacing 2^i in pass i, `iterations` of 1..5
+ * passes) of a beauty target, guided by the feature buffers pt_set_feature_targets accumulated beside it. All four
+ * textures are RGBA32F render targets of `ctx` (wrapped ones included) of one size; dst differs from the inputs.
+ * Per pixel: w = albedo_weight.w, valid = w > 0, n = normal_id.xyz / w, id = normal_id.w, a = albedo_weight.xyz / w,
+ * c = beauty.xyz / w, and d = demodulate ? c / max(a, 1e-3) : c. Each pass replaces d of a valid pixel by the
+ * mean of the valid taps of its own id inside the image, weighted K[|dx|] K[|dy|] exp(-(|n_p - n_q|^2 /
+ * sigma_normal^2 + |d_p - d_q|^2 / sigma_c^2)) with K = {3/8, 1/4, 1/16} and sigma_c = sigma_colour / 2^i. Then
+ * dst = (d * max(a, 1e-3) if demodulated, else d) * w, dst.w = 1; an invalid pixel is (0, 0, 0, 1). So dst is in
+ * the accumulation's scale with every sharpness flag saying "do not blur": screenOutput with dst bound as
+ * accumulationBuffer is a plain tone map of it. Operation by operation: INTEGRATION.md "Denoising". A tap that
+ * is skipped contributes nothing whatever it holds; a NaN in a valid pixel spreads over its footprint.
+ * Asynchronous: enqueued on the context's stream after everything queued so far (a deferred screenCopy runs
+ * first, as for any observer), before any later read or pt_sync; it does not synchronise, writes none of its
+ * three inputs and changes no counter, statistic or timing window. Under pt_set_row_partition it filters the whole
+ * frame, as screenOutput does by default: the caller supplies complete inputs.
+ * PT_ERR_ARG, before any device work: a bad handle, a texture of another context or not a render target, sizes
+ * that differ, dst equal to an input, iterations outside 1..5, a sigma that is not finite and > 0, demodulate
+ * other than 0 or 1. PT_ERR_UNSUPPORTED: a context of several parts - its targets are distributed by 16-row
+ * bands and the filter's footprint reaches +-32 rows; filtering across parts is out of scope. */
+int pt_denoise(pt_ctx* ctx, const pt_texture* beauty, const pt_texture* normal_id,
+               const pt_texture* albedo_weight, pt_texture* dst,
+               int iterations, float sigma_normal, float sigma_colour, int demodulate);
 /* Device self-test of the pinned GLSL built-ins (ops as the oracle's pto_math_probe). */
 int pt_math_probe(pt_ctx* ctx, int op, const float* x, const float* y, float* out, int n);
 /* Exhaustive device self-test of a fast built-in sequence against the IEEE operation it replaces,

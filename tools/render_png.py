@@ -7,7 +7,11 @@ With --features DIR the accumulated G-buffer (Effect.setFeatureTargets) is saved
 (xyz / weight * 0.5 + 0.5), albedo.png (xyz / weight) and id.png (the last frame's object id, modulo a small
 palette).
 
-usage: render_png.py [--workload dragon|bunny|helmet] [--size WxH] [--frames K] [--features DIR] --out PATH"""
+With --denoise the accumulation is also filtered by Engine.denoise (pt_denoise, default parameters) over the feature
+buffers and drawn by the same screenOutput with the result bound as its accumulation sampler - a plain tone map of
+it; saved beside the plain image as <out>_denoised.png.
+
+usage: render_png.py [--workload dragon|bunny|helmet] [--size WxH] [--frames K] [--features DIR] [--denoise] --out PATH"""
 import argparse
 import os
 import sys
@@ -28,6 +32,7 @@ ap.add_argument("--size", default="1920x1080")
 ap.add_argument("--frames", type=int, default=256)
 ap.add_argument("--out", required=True)
 ap.add_argument("--features", metavar="DIR", help="also save normal.png, albedo.png and id.png there")
+ap.add_argument("--denoise", action="store_true", help="also save the denoised image as <out>_denoised.png")
 a = ap.parse_args()
 W, Hh = (int(v) for v in a.size.lower().split("x"))
 meta = H.stream("hdri_helmet_320x180" if a.workload == "helmet" else "gltf_bunny_1080p")
@@ -40,7 +45,7 @@ if a.workload == "helmet":
         p.textures[sampler] = bp.Texture(e, maps[kind], name=kind)
 e.resize_canvas(W, Hh)
 feat = None
-if a.features:
+if a.features or a.denoise:
     feat = (bp.RenderTargetTexture("featureNormalId", (W, Hh), e), bp.RenderTargetTexture("featureAlbedoWeight", (W, Hh), e))
     p.wrappers[H.path_call(p.meta["frames"][0])["effect"]].effect.setFeatureTargets(*feat)
 for call in p.meta["frames"][0]:
@@ -55,7 +60,7 @@ dt = time.perf_counter() - t0
 img = e.read_canvas(W, Hh)[::-1, :, :3]          # GL rows bottom-up -> image rows top-down
 from PIL import Image                             # noqa: E402
 Image.fromarray(np.ascontiguousarray(img)).save(a.out)
-if feat:
+if a.features:
     PALETTE = np.array([[0, 0, 0], [230, 25, 75], [60, 180, 75], [255, 225, 25], [0, 130, 200], [245, 130, 48],
                         [145, 30, 180], [70, 240, 240], [240, 50, 230], [210, 245, 60], [250, 190, 212], [0, 128, 128]], np.uint8)
     nid, alb = (t.read()[::-1] for t in feat)
@@ -70,5 +75,14 @@ if feat:
     Image.fromarray(np.ascontiguousarray(PALETTE[nid[..., 3].astype(np.int64) % len(PALETTE)])).save(os.path.join(a.features, "id.png"))
     print("features: weight %.1f, %d object ids, saved normal.png albedo.png id.png in %s" % (
         float(alb[0, 0, 3]), len(np.unique(nid[..., 3])), a.features))
+if a.denoise:
+    p.textures["denoised"] = bp.RenderTargetTexture("denoised", (W, Hh), e)
+    e.denoise(p.textures["pathTracingRenderTarget"], feat[0], feat[1], p.textures["denoised"])
+    output = dict(H.output_call(p.synth_frame(a.frames - 1)))
+    output["samplers"] = {k: "denoised" for k in output["samplers"]}
+    p.play_call(output)
+    stem, ext = os.path.splitext(a.out)
+    Image.fromarray(np.ascontiguousarray(e.read_canvas(W, Hh)[::-1, :, :3])).save(stem + "_denoised" + ext)
+    print("denoised: saved %s" % (stem + "_denoised" + ext))
 print("%s %dx%d %d frames: %.1f Mpaths/s, mean %.1f, saved %s" % (a.workload, W, Hh, a.frames,
       W * Hh * a.frames / dt / 1e6, img.mean(), a.out))
