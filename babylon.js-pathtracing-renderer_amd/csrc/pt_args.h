@@ -242,7 +242,11 @@ struct BlendArgs {
 // pt_feature_fold: a draw's G-buffer sample folded into the effect's feature targets in place, over the owned
 // 16-row bands, by the beauty's history rule (include/pt.h pt_set_feature_targets). g0 / g1: the staged sample
 // (normal.xyz, id | colour.xyz, -), `stride` pixels per row: the megakernel's staging slab (the target's
-// width) or the queued backends' per-pixel G-buffer (WfBufs::gb0 / gb1, the quad-rounded width)
+// width) or the queued backends' per-pixel G-buffer (WfBufs::gb0 / gb1, the quad-rounded width).
+// The moments target (include/pt.h pt_set_moment_target) folds the luminance of the draw's radiance and its
+// square from `rad` (TraceArgs::rad at the target's width, WfBufs::rad at the quad-rounded one) in the same launch;
+// with it bound, g0 / g1 are read only for a feature target that is bound too: a draw with the moments target
+// alone stages no G-buffer (both NULL).
 struct FoldArgs {
     int width, height;
     int num_parts, part;
@@ -253,6 +257,9 @@ struct FoldArgs {
     int stride;
     float4* normal_id;       // NULL: not produced
     float4* albedo_weight;   // NULL: not produced
+    const float4* rad;       // the draw's radiance (xyz), `rad_stride` pixels per row
+    int rad_stride;
+    float4* moments;         // NULL: not produced
 };
 
 // (PT_CONT_SORT) pt_cont's records ordered by a ray key (pt_kernels.hip pt_cont_hist / pt_cont_scatter)
@@ -288,6 +295,26 @@ struct DenoiseArgs {
     float4* dst;
     float4* colour[2];
     float4* guide;
+};
+
+// pt_denoise_variance (pt_denoise_var.hip): the same filter with a luminance edge-stop scaled by each pixel's own
+// variance, which the passes filter along with the colour. The host carves three float4 planes and two float
+// planes of width * height out of one slab: colour[2] = {d.xyz, id} and var[2], the passes' ping-pong (pass i reads
+// [i & 1]), and guide = {n.xyz, valid}, which no pass changes: a tap costs 36 B.
+struct DenoiseVarArgs {
+    int width, height;
+    int iterations;         // 1..5: pass i taps at spacing 2^i
+    int demodulate;         // 0 | 1
+    float inv_n;            // 1 / sigma_normal^2
+    float sl2;              // sigma_luminance^2
+    const float4* beauty;
+    const float4* normal_id;
+    const float4* albedo_weight;
+    const float4* moments;
+    float4* dst;
+    float4* colour[2];
+    float4* guide;
+    float* var[2];
 };
 
 } // namespace pt

@@ -22,6 +22,7 @@
 //   SCREEN_OUTPUT   -> pt_output into the canvas (RGBA8) or an RGBA32F target, with a deferred copy
 //                      and order build riding along.
 // dev_denoise (pt_denoise) is no draw: the à-trous filter's prep and passes (pt_denoise.hip) on the main stream.
+// dev_denoise_variance (pt_denoise_variance) likewise (pt_denoise_var.hip), with a slab of its own.
 // The main stream is the context's own or the caller's (dev_set_stream); per-draw timing events are off
 // until asked for (pt_last_render_ms, the timing window).
 #include "../../include/pt.h"
@@ -56,6 +57,7 @@ hipError_t pt_launch_cont_sort(const pt::SortArgs* a, size_t cap, hipStream_t s)
 hipError_t pt_launch_cont(int prog, const pt::TraceArgs* a, int waves, hipStream_t s);
 hipError_t pt_launch_output(const pt::OutputArgs* a, hipStream_t s, int waves);
 hipError_t pt_launch_denoise(const pt::DenoiseArgs* a, hipStream_t s);
+hipError_t pt_launch_denoise_var(const pt::DenoiseVarArgs* a, hipStream_t s);
 hipError_t pt_launch_math_probe(int op, const float* x, const float* y, float* out, int n, hipStream_t s);
 hipError_t pt_launch_persist(int prog, int count, const pt::TraceArgs* a, const pt::WfBufs* w, int tiles_x,
                              unsigned n_wave_tiles, unsigned per_wave, unsigned refill, hipStream_t s);
@@ -106,7 +108,8 @@ struct DevFx {
     int prog = PT_PROG_UNKNOWN;
     std::unordered_map<std::string, Uniform> uniforms;
     std::unordered_map<std::string, DevTex*> samplers;
-    DevTex* feat[2] = {};   // feature targets (dev_set_feature_targets): normal + id, albedo + weight
+    DevTex* feat[3] = {};   // feature targets (dev_set_feature_targets): normal + id, albedo + weight; [2] the
+                            // luminance moments (dev_set_moment_target)
 };
 
 struct Dev {
@@ -136,8 +139,8 @@ struct Dev {
     // pt::spill_slab), RAD rad[sets()], radiance + flag (pixels), FEAT feat[sets()][2], the G-buffer pt_trace stages
     // for pt_feature_fold, once a draw has feature targets bound (pixels), CONT pt_cont's records (records per
     // buffer set; pt::ContLayout), GB the persistent backend's G-buffer + radiance (pixels), DENOISE pt_denoise's
-    // three planes, colour[2] + guide (pixels)
-    enum Slab { WF, LPT, SPILL, RAD, FEAT, CONT, GB, DENOISE, kSlabs };
+    // three planes, colour[2] + guide (pixels), DENOISE_VAR pt_denoise_variance's, those and var[2] (pixels)
+    enum Slab { WF, LPT, SPILL, RAD, FEAT, CONT, GB, DENOISE, DENOISE_VAR, kSlabs };
     DevMem slab[kSlabs];
     pt::WfBufs wf = {};
     size_t wf_pixels = 0, wf_spill = 0;
@@ -714,7 +717,7 @@ int feature_check(const DevFx* fx, const DevTex* target)
 {
     Dev* c = fx->ctx;
     const DevTex* prev = sampler(fx, "previousBuffer");
-    for (int k = 0; k < 2; k++) {
+    for (int k = 0; k < 3; k++) {
         const DevTex* t = fx->feat[k];
         if (!t) continue;
         if (t->w != target->w || t->h != target->h)
@@ -724,14 +727,20 @@ int feature_check(const DevFx* fx, const DevTex* target)
     }
     if (fx->feat[0] && fx->feat[1] && (fx->feat[0] == fx->feat[1] || fx->feat[0]->d == fx->feat[1]->d))
         return fail(c, PT_ERR_STATE, "the two feature targets must be distinct");
+    for (int k = 0; k < 2; k++)
+        if (fx->feat[2] && fx->feat[k] && (fx->feat[2] == fx->feat[k] || fx->feat[2]->d == fx->feat[k]->d))
+            return fail(c, PT_ERR_STATE, "the moments target must not be another feature target");
     return PT_OK;
 }
 
-// the feature fold of a draw, from the G-buffer staged at g0 / g1 (`stride` pixels per row)
-pt::FoldArgs fold_args(const DevFx* fx, const pt::TraceArgs& a, const float4* g0, const float4* g1, int stride)
+// the feature fold of a draw, from the G-buffer staged at g0 / g1 (`stride` pixels per row) and, for the moments
+// target, the draw's radiance at `rad` (`rad_stride` pixels per row)
+pt::FoldArgs fold_args(const DevFx* fx, const pt::TraceArgs& a, const float4* g0, const float4* g1, int stride,
+                       const float4* rad, int rad_stride)
 {
     return pt::FoldArgs{ a.width, a.height, a.num_parts, a.part, a.frame, a.moving, g0, g1, stride,
-                         fx->feat[0] ? (float4*)fx->feat[0]->d : nullptr, fx->feat[1] ? (float4*)fx->feat[1]->d : nullptr };
+                         fx->feat[0] ? (float4*)fx->feat[0]->d : nullptr, fx->feat[1] ? (float4*)fx->feat[1]->d : nullptr,
+                         rad, rad_stride, fx->feat[2] ? (float4*)fx->feat[2]->d : nullptr };
 }
 
 // The wavefront / persistent schedules (and a draw that owns no band) over gx x gy tiles: on the main stream,
@@ -768,9 +777,9 @@ int draw_queued(DevFx* fx, DevTex* target, pt::TraceArgs& a, bool mesh, int gx, 
     }
     if (int erc = end_draw(c, fx->prog)) return erc;
     // feature targets: folded from the backend's per-pixel G-buffer (quad-rounded rows), after its finish pass
-    if (gy > 0 && c->backend != PT_BACKEND_MEGAKERNEL && (fx->feat[0] || fx->feat[1])) {
+    if (gy > 0 && c->backend != PT_BACKEND_MEGAKERNEL && (fx->feat[0] || fx->feat[1] || fx->feat[2])) {
         const pt::WfBufs& w = c->backend == PT_BACKEND_WAVEFRONT ? c->wf : c->gb;
-        const pt::FoldArgs f = fold_args(fx, a, w.gb0, w.gb1, w.wq);
+        const pt::FoldArgs f = fold_args(fx, a, w.gb0, w.gb1, w.wq, w.rad, w.wq);
         HIPCHK(c, pt_launch_feature_fold(&f, gy, c->stream, 0));
     }
     return PT_OK;
@@ -887,8 +896,10 @@ int draw_mega(DevFx* fx, DevTex* target, pt::TraceArgs& a, bool mesh, int gx, in
     pt::BlendArgs b{ a.width, a.height, a.num_parts, a.part, a.frame, a.moving, a.rad, a.prev, a.out, a.cont_count, a.cont_bins };
     HIPCHK(c, pt_launch_blend(&b, gy, c->stream, g.one_wave ? c->k.main_waves : 0));
     // ---- feature targets: the staged G-buffer folded right after, on the main stream too, so folds keep the draws' order
-    if (feat) {
-        const pt::FoldArgs f = fold_args(fx, a, a.feat0, a.feat1, a.width);
+    // (the moments target alone stages nothing: the fold reads the set's rad, which every pt_trace variant writes.
+    // The set's next writer, draw k + sets, waits for the mark draw k + 1 records on this stream, after this fold.)
+    if (feat || fx->feat[2]) {
+        const pt::FoldArgs f = fold_args(fx, a, a.feat0, a.feat1, a.width, a.rad, a.width);
         HIPCHK(c, pt_launch_feature_fold(&f, gy, c->stream, g.one_wave ? c->k.main_waves : 0));
     }
 
@@ -1554,6 +1565,18 @@ int dev_set_feature_targets(DevFx* fx, DevTex* normal_id, DevTex* albedo_weight)
     return PT_OK;
 }
 
+int dev_set_moment_target(DevFx* fx, DevTex* moments)
+{
+    if (!fx) return PT_ERR_ARG;
+    Dev* c = fx->ctx;
+    if (fx->prog == PT_PROG_SCREEN_COPY || fx->prog == PT_PROG_SCREEN_OUTPUT)
+        return fail(c, PT_ERR_ARG, "the moments target needs a path-tracing effect");
+    if (moments && (moments->ctx != c || moments->kind != TEX_RT))
+        return fail(c, PT_ERR_ARG, "the moments target must be a render target of this context");
+    fx->feat[2] = moments;
+    return PT_OK;
+}
+
 // pt_denoise: checked here, then prep and the passes on the main stream, where every draw's blend and feature fold
 // are (the side streams' path tracing reads and writes none of the four textures); no timing events, no counters
 int dev_denoise(Dev* c, const DevTex* beauty, const DevTex* normal_id, const DevTex* albedo_weight, DevTex* dst,
@@ -1592,6 +1615,50 @@ int dev_denoise(Dev* c, const DevTex* beauty, const DevTex* normal_id, const Dev
     a.colour[1] = a.colour[0] + mem.size;
     a.guide = a.colour[1] + mem.size;
     HIPCHK(c, pt_launch_denoise(&a, c->stream));
+    return PT_OK;
+}
+
+// pt_denoise_variance: as dev_denoise, with the moments among the inputs and a slab of its own (56 B per pixel)
+int dev_denoise_variance(Dev* c, const DevTex* beauty, const DevTex* normal_id, const DevTex* albedo_weight,
+                         const DevTex* moments, DevTex* dst, int iterations, float sigma_normal, float sigma_luminance,
+                         int demodulate)
+{
+    if (!c) return PT_ERR_ARG;
+    const DevTex* const in[4] = { beauty, normal_id, albedo_weight, moments };
+    if (!dst || dst->ctx != c || dst->kind != TEX_RT) return fail(c, PT_ERR_ARG, "pt_denoise_variance: dst must be a render target of this context");
+    for (const DevTex* t : in) {
+        if (!t || t->ctx != c || t->kind != TEX_RT) return fail(c, PT_ERR_ARG, "pt_denoise_variance: the inputs must be render targets of this context");
+        if (t->w != dst->w || t->h != dst->h) return fail(c, PT_ERR_ARG, "pt_denoise_variance: the five textures must have one size");
+        if (t == dst || t->d == dst->d) return fail(c, PT_ERR_ARG, "pt_denoise_variance: dst must not be an input");
+    }
+    if (iterations < 1 || iterations > 5) return fail(c, PT_ERR_ARG, "pt_denoise_variance: iterations must be 1..5");
+    if (!(std::isfinite(sigma_normal) && sigma_normal > 0.0f && std::isfinite(sigma_luminance) && sigma_luminance > 0.0f))
+        return fail(c, PT_ERR_ARG, "pt_denoise_variance: the sigmas must be finite and > 0");
+    if (demodulate != 0 && demodulate != 1) return fail(c, PT_ERR_ARG, "pt_denoise_variance: demodulate must be 0 or 1");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = flush_copy(c)) return rc;
+    const size_t pixels = (size_t)dst->w * dst->h;
+    DevMem& mem = c->slab[Dev::DENOISE_VAR];
+    if (pixels > mem.size)
+        if (int rc = mem.grow(c, pixels, pixels * (3 * sizeof(float4) + 2 * sizeof(float)), WAIT_MAIN, false)) return rc;
+    pt::DenoiseVarArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.width = dst->w; a.height = dst->h;
+    a.iterations = iterations;
+    a.demodulate = demodulate;
+    a.inv_n = 1.0f / (sigma_normal * sigma_normal);
+    a.sl2 = sigma_luminance * sigma_luminance;
+    a.beauty = (const float4*)beauty->d;
+    a.normal_id = (const float4*)normal_id->d;
+    a.albedo_weight = (const float4*)albedo_weight->d;
+    a.moments = (const float4*)moments->d;
+    a.dst = (float4*)dst->d;
+    a.colour[0] = mem.as<float4>();
+    a.colour[1] = a.colour[0] + mem.size;
+    a.guide = a.colour[1] + mem.size;
+    a.var[0] = (float*)(a.guide + mem.size);
+    a.var[1] = a.var[0] + mem.size;
+    HIPCHK(c, pt_launch_denoise_var(&a, c->stream));
     return PT_OK;
 }
 

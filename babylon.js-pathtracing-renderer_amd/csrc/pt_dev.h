@@ -67,6 +67,10 @@ int dev_cont_stats(Dev* c, uint64_t out[2]);
 int dev_set_feature_targets(DevFx* fx, DevTex* normal_id, DevTex* albedo_weight);
 int dev_denoise(Dev* c, const DevTex* beauty, const DevTex* normal_id, const DevTex* albedo_weight, DevTex* dst,
                 int iterations, float sigma_normal, float sigma_colour, int demodulate);
+int dev_set_moment_target(DevFx* fx, DevTex* moments);
+int dev_denoise_variance(Dev* c, const DevTex* beauty, const DevTex* normal_id, const DevTex* albedo_weight,
+                         const DevTex* moments, DevTex* dst, int iterations, float sigma_normal, float sigma_luminance,
+                         int demodulate);
 int dev_math_exhaustive(Dev* c, int op, uint64_t* mismatches);
 int dev_math_probe(Dev* c, int op, const float* x, const float* y, float* out, int n);
 

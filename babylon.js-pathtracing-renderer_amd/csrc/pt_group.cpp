@@ -683,6 +683,32 @@ int pt_denoise(pt_ctx* c, const pt_texture* beauty, const pt_texture* normal_id,
                                   iterations, sigma_normal, sigma_colour, demodulate));
 }
 
+int pt_set_moment_target(pt_effect* fx, pt_texture* moments)
+{
+    if (!fx) return PT_ERR_ARG;
+    pt_ctx* c = fx->ctx;
+    if (!is_trace(fx->prog)) return fail(c, PT_ERR_ARG, "the moments target needs a path-tracing effect");
+    if (moments && (moments->ctx != c || moments->kind != TEX_RT))
+        return fail(c, PT_ERR_ARG, "the moments target must be a render target of this context");
+    // (every part folds its own bands into its share of the target, as for the feature targets)
+    return each(c, [&](int k) { return dev_set_moment_target(fx->sub[k], moments ? moments->sub[k] : nullptr); });
+}
+
+int pt_denoise_variance(pt_ctx* c, const pt_texture* beauty, const pt_texture* normal_id, const pt_texture* albedo_weight,
+                        const pt_texture* moments, pt_texture* dst, int iterations, float sigma_normal,
+                        float sigma_luminance, int demodulate)
+{
+    if (!c) return PT_ERR_ARG;
+    for (const pt_texture* t : { beauty, normal_id, albedo_weight, moments, (const pt_texture*)dst })
+        if (!t || t->ctx != c || t->kind != TEX_RT)
+            return fail(c, PT_ERR_ARG, "pt_denoise_variance takes five render targets of this context");
+    // (as pt_denoise: a part's targets hold its own bands only, and the taps reach +-32 rows)
+    if (c->n() > 1) return fail(c, PT_ERR_UNSUPPORTED, "pt_denoise_variance needs a one-part context");
+    return take(c, 0, dev_denoise_variance(c->parts[0], beauty->sub[0], normal_id->sub[0], albedo_weight->sub[0],
+                                           moments->sub[0], dst->sub[0], iterations, sigma_normal, sigma_luminance,
+                                           demodulate));
+}
+
 int pt_math_probe(pt_ctx* c, int op, const float* x, const float* y, float* out, int n)
 {
     if (!c) return PT_ERR_ARG;

@@ -4,8 +4,9 @@
 //                         with the Cornell / glTF scene shaders' SetupScene, SceneIntersect and
 //                         CalculateRadiance). One lane = one pixel = one path of <= 6 segments.
 //   pt_copy               screenCopy (js/PathTracingCommon.js:1-16), band-aware.
-//   pt_feature_fold       a draw's G-buffer sample folded into the bound feature targets (normal + id,
-//                         albedo + weight) by the accumulation's history rule.
+//   pt_feature_fold<MOM>  a draw's G-buffer sample folded into the bound feature targets (normal + id,
+//                         albedo + weight) by the accumulation's history rule; MOM: and its radiance's
+//                         luminance moments into the moments target.
 //   pt_output             screenOutput (js/PathTracingCommon.js:19-309): 5x5 / 3x3 edge-aware
 //                         filter, 1/N, Reinhard, gamma 0.4545, unorm8.
 //   pt_math_probe_kernel  device self-test of the pinned built-ins.
@@ -251,23 +252,32 @@ __global__ __launch_bounds__(64) void pt_blend_w(BlendArgs a, int units_x, int u
 // A draw's G-buffer sample folded into the effect's feature targets (pt_set_feature_targets), in place, by
 // the rule of the accumulation above: history 0 at frame 1 (+0.0, still added), history and sample halved
 // while the camera moves. One IEEE multiply per product and one add per component (-ffp-contract=off).
-// normal_id.w is this draw's objectID, albedo_weight.w the weight of the samples held. Four rows of a band
+// normal_id.w is this draw's objectID, albedo_weight.w the weight of the samples held. The moments target
+// (pt_set_moment_target) takes the luminance L of the draw's radiance: (sum L, sum L^2, +0.0, weight), one more
+// streamed plane read and written in the same launch (MOM; without it the code is what it was before that target
+// existed: 70 VGPRs, 7 waves per SIMD). Four rows of a band
 // per thread as blendRows; every access is 16 B per lane, coalesced along the row; loads first.
+template <bool MOM>
 PT_D void foldRows(const FoldArgs& a, int x, int r0)
 {
     typedef float nt4 __attribute__((ext_vector_type(4)));
     const bool reset = a.frame == 1.0f;
     const float f = (!reset && a.moving) ? 0.5f : 1.0f;
-    nt4 g0[4], g1[4], on[4], oa[4];
+    nt4 g0[4], g1[4], on[4], oa[4], rv[4], om[4];
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         const int y = r0 + 4 * k;
         if (y < a.height) {
             const long long j = (long long)y * a.stride + x, i = (long long)y * a.width + x;
-            g0[k] = __builtin_nontemporal_load((const nt4*)&a.g0[j]);
-            g1[k] = __builtin_nontemporal_load((const nt4*)&a.g1[j]);
+            // (with the moments target alone no G-buffer was staged: g0 / g1 are NULL)
+            if (!MOM || a.normal_id) g0[k] = __builtin_nontemporal_load((const nt4*)&a.g0[j]);
+            if (!MOM || a.albedo_weight) g1[k] = __builtin_nontemporal_load((const nt4*)&a.g1[j]);
             if (a.normal_id) on[k] = __builtin_nontemporal_load((const nt4*)&a.normal_id[i]);
             if (a.albedo_weight) oa[k] = __builtin_nontemporal_load((const nt4*)&a.albedo_weight[i]);
+            if (MOM) {
+                rv[k] = __builtin_nontemporal_load((const nt4*)&a.rad[(long long)y * a.rad_stride + x]);
+                om[k] = __builtin_nontemporal_load((const nt4*)&a.moments[i]);
+            }
         }
     }
 #pragma unroll
@@ -284,19 +294,25 @@ PT_D void foldRows(const FoldArgs& a, int x, int r0)
             const nt4 o = { fold(oa[k].x, g1[k].x), fold(oa[k].y, g1[k].y), fold(oa[k].z, g1[k].z), fold(oa[k].w, 1.0f) };
             __builtin_nontemporal_store(o, (nt4*)&a.albedo_weight[i]);
         }
+        if (MOM) {   // the luminance of the draw's radiance and its square (pt_set_moment_target)
+            const float L = (0.2126f * rv[k].x + 0.7152f * rv[k].y) + 0.0722f * rv[k].z;
+            const nt4 o = { fold(om[k].x, L), fold(om[k].y, L * L), 0.0f, fold(om[k].w, 1.0f) };
+            __builtin_nontemporal_store(o, (nt4*)&a.moments[i]);
+        }
     }
 }
 // On the main stream right after the draw's pt_blend (or the queued backends' finish pass, from their per-pixel
 // G-buffer), so folds keep the draws' order while their path tracing overlaps: one-wave workgroups that stride
 // over (64 columns x 4 rows of a band) units, as pt_blend_w. (Fused into pt_blend_w as one launch it measured
 // the same: DESIGN.md §6.) The targets are streamed too: nothing reads them before the next draw's fold.
+template <bool MOM>
 __global__ __launch_bounds__(64) void pt_feature_fold(FoldArgs a, int units_x, int units)
 {
     for (int u = blockIdx.x; u < units; u += gridDim.x) {
         const int cx = u % units_x, rest = u / units_x;
         const int band = (rest >> 2) * a.num_parts + a.part;
         const int x = cx * 64 + threadIdx.x;
-        if (x < a.width) foldRows(a, x, band * kTile + (rest & 3));
+        if (x < a.width) foldRows<MOM>(a, x, band * kTile + (rest & 3));
     }
 }
 
@@ -663,7 +679,9 @@ hipError_t pt_launch_feature_fold(const pt::FoldArgs* a, int bands, hipStream_t 
 {
     if (bands <= 0 || a->width <= 0) return hipSuccess;
     const int ux = (a->width + 63) / 64, units = ux * bands * 4;
-    hipLaunchKernelGGL(pt::pt_feature_fold, dim3(waves > 0 && waves < units ? waves : units), dim3(64), 0, s, *a, ux, units);
+    const dim3 grid(waves > 0 && waves < units ? waves : units);
+    if (a->moments) hipLaunchKernelGGL(pt::pt_feature_fold<true>, grid, dim3(64), 0, s, *a, ux, units);
+    else hipLaunchKernelGGL(pt::pt_feature_fold<false>, grid, dim3(64), 0, s, *a, ux, units);
     return hipGetLastError();
 }
 

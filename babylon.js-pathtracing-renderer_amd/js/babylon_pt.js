@@ -21,6 +21,8 @@
 //   new BABYLON.EffectRenderer(engine).render()   -> pt_render (:1230-1235)
 //   effect.setFeatureTargets(normalRT, albedoRT)  -> pt_set_feature_targets (extension: accumulated G-buffer)
 //   engine.denoise(beautyRT, normalRT, albedoRT, dstRT, opts) -> pt_denoise (extension: a-trous filter over them)
+//   effect.setMomentTarget(momentsRT)             -> pt_set_moment_target (extension: accumulated luminance moments)
+//   engine.denoiseVariance(beautyRT, normalRT, albedoRT, momentsRT, dstRT, opts) -> pt_denoise_variance
 'use strict';
 const fs = require('fs');
 const path = require('path');
@@ -198,6 +200,16 @@ function install(BABYLON, opts) {
         o.iterations === undefined ? 3 : o.iterations | 0, o.sigmaNormal === undefined ? 0.5 : +o.sigmaNormal,
         o.sigmaColour === undefined ? 1.0 : +o.sigmaColour, o.demodulate === undefined || o.demodulate ? 1 : 0), 'denoise');
     }
+    // MI355X extension (pt_denoise_variance): the same filter with a luminance edge-stop scaled by each pixel's
+    // own variance, from the moments accumulated by effect.setMomentTarget; `dst` as for denoise.
+    // o: { iterations = 3, sigmaNormal = 0.5, sigmaLuminance = 4.0, demodulate = true }. Asynchronous.
+    denoiseVariance(beauty, normalRT, albedoRT, momentsRT, dst, o) {
+      o = o || {};
+      const pt = (t) => (t ? t._pt : null);
+      return check(this._pt, addon.pt_denoise_variance(this._pt, pt(beauty), pt(normalRT), pt(albedoRT), pt(momentsRT), pt(dst),
+        o.iterations === undefined ? 3 : o.iterations | 0, o.sigmaNormal === undefined ? 0.5 : +o.sigmaNormal,
+        o.sigmaLuminance === undefined ? 4.0 : +o.sigmaLuminance, o.demodulate === undefined || o.demodulate ? 1 : 0), 'denoiseVariance');
+    }
     dispose() { if (this._pt) { addon.pt_ctx_destroy(this._pt); this._pt = null; } super.dispose(); }
   }
 
@@ -342,6 +354,13 @@ function install(BABYLON, opts) {
         check(this._ctx, addon.pt_set_feature_targets(this._pt, normalRT ? normalRT._pt : null, albedoRT ? albedoRT._pt : null),
           'setFeatureTargets');
       }
+      return this;
+    }
+    // MI355X extension (pt_set_moment_target): while a RenderTargetTexture is bound here, every draw of this
+    // path-tracing effect also accumulates the luminance L of its radiance into it in place, by the beauty's
+    // history rule: momentsRT = (sum of L, sum of L^2, 0, weight). null / undefined unbinds it
+    setMomentTarget(momentsRT) {
+      if (this._pt) check(this._ctx, addon.pt_set_moment_target(this._pt, momentsRT ? momentsRT._pt : null), 'setMomentTarget');
       return this;
     }
   }

@@ -16,7 +16,7 @@
 
 #include "pt.h"
 
-#define MAXARGS 9
+#define MAXARGS 10
 #define CHECK(call) do { if ((call) != napi_ok) { napi_throw_error(env, NULL, #call " failed"); return NULL; } } while (0)
 
 static napi_value num(napi_env env, double v) { napi_value r; napi_create_double(env, v, &r); return r; }
@@ -389,6 +389,22 @@ static napi_value Denoise(napi_env env, napi_callback_info info)
                                (pt_texture*)handle(env, a[4]), i32(env, a[5]), (float)f64(env, a[6]),
                                (float)f64(env, a[7]), i32(env, a[8])));
 }
+/* pt_set_moment_target(effect, moments | null) -> status */
+static napi_value SetMomentTarget(napi_env env, napi_callback_info info)
+{
+    napi_value a[MAXARGS]; if (args(env, info, a, 1) < 0) return NULL;
+    return num(env, pt_set_moment_target((pt_effect*)handle(env, a[0]), (pt_texture*)handle(env, a[1])));
+}
+/* pt_denoise_variance(ctx, beauty, normalId, albedoWeight, moments, dst, iterations, sigmaNormal, sigmaLuminance,
+ * demodulate) -> status */
+static napi_value DenoiseVariance(napi_env env, napi_callback_info info)
+{
+    napi_value a[MAXARGS]; if (args(env, info, a, 10) < 0) return NULL;
+    return num(env, pt_denoise_variance((pt_ctx*)handle(env, a[0]), (const pt_texture*)handle(env, a[1]),
+                                        (const pt_texture*)handle(env, a[2]), (const pt_texture*)handle(env, a[3]),
+                                        (const pt_texture*)handle(env, a[4]), (pt_texture*)handle(env, a[5]),
+                                        i32(env, a[6]), (float)f64(env, a[7]), (float)f64(env, a[8]), i32(env, a[9])));
+}
 /* pt_bvh_build(aabbIn: Float32Array (9 per triangle), work: Uint32Array, out: Float32Array) -> node count */
 static napi_value BvhBuild(napi_env env, napi_callback_info info)
 {
@@ -466,6 +482,7 @@ static napi_value Init(napi_env env, napi_value exports)
         { "pt_timing_latency", TimingLatency },
         { "pt_set_counting", SetCounting }, { "pt_read_counters", ReadCounters }, { "pt_reset_counters", ResetCounters }, { "pt_queue_stats", QueueStats }, { "pt_cont_stats", ContStats },
         { "pt_set_feature_targets", SetFeatureTargets }, { "pt_denoise", Denoise },
+        { "pt_set_moment_target", SetMomentTarget }, { "pt_denoise_variance", DenoiseVariance },
         { "pt_bvh_build", BvhBuild }, { "pt_bvh_build_gpu", BvhBuildGpu },
         { "pt_jpeg_size", JpegSize }, { "pt_jpeg_decode_rgba8", JpegDecode }, { "pt_version", Version },
     };

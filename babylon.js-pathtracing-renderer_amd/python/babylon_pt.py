@@ -40,7 +40,7 @@ SYMBOLS = [
     "pt_render_target_resize", "pt_texture_size", "pt_texture_destroy",
     "pt_render", "pt_read_pixels", "pt_write_pixels",
     "pt_set_row_partition", "pt_set_output_partition", "pt_canvas_wrap", "pt_set_backend", "pt_set_bvh_layout", "pt_bvh_layout_used", "pt_set_stream", "pt_texture_device_ptr", "pt_last_render_ms", "pt_timing_begin", "pt_timing_end", "pt_timing_latency",
-    "pt_set_counting", "pt_read_counters", "pt_reset_counters", "pt_queue_stats", "pt_cont_stats", "pt_set_feature_targets", "pt_denoise", "pt_math_probe", "pt_math_exhaustive", "pt_bvh_build", "pt_bvh_build_gpu", "pt_jpeg_size", "pt_jpeg_decode_rgba8", "pt_version",
+    "pt_set_counting", "pt_read_counters", "pt_reset_counters", "pt_queue_stats", "pt_cont_stats", "pt_set_feature_targets", "pt_denoise", "pt_set_moment_target", "pt_denoise_variance", "pt_math_probe", "pt_math_exhaustive", "pt_bvh_build", "pt_bvh_build_gpu", "pt_jpeg_size", "pt_jpeg_decode_rgba8", "pt_version",
 ]
 
 _lib = None
@@ -92,6 +92,8 @@ def lib():
         "pt_cont_stats": ([vp, ctypes.POINTER(ctypes.c_uint64)], i32),
         "pt_set_feature_targets": ([vp, vp, vp], i32),
         "pt_denoise": ([vp, vp, vp, vp, vp, i32, ctypes.c_float, ctypes.c_float, i32], i32),
+        "pt_set_moment_target": ([vp, vp], i32),
+        "pt_denoise_variance": ([vp, vp, vp, vp, vp, vp, i32, ctypes.c_float, ctypes.c_float, i32], i32),
         "pt_queue_stats": ([vp, ctypes.POINTER(ctypes.c_uint32)], i32), "pt_version": ([], ctypes.c_char_p),
     }
     for name, (args, res) in sig.items():
@@ -251,6 +253,16 @@ class Engine:
         tone-maps it unchanged. Asynchronous, on the engine's stream after everything queued so far."""
         self.check(lib().pt_denoise(self.ctx, beauty.handle, normal_id.handle, albedo_weight.handle, dst.handle,
                                     int(iterations), float(sigma_normal), float(sigma_colour), int(demodulate)), "pt_denoise")
+
+    def denoise_variance(self, beauty, normal_id, albedo_weight, moments, dst, iterations=3, sigma_normal=0.5,
+                         sigma_luminance=4.0, demodulate=True):
+        """MI355X extension (pt_denoise_variance): the a-trous filter of `beauty` with a luminance edge-stop scaled
+        by each pixel's own variance, from the luminance moments accumulated beside the feature targets
+        (Effect.setMomentTarget), into the render target `dst`, in the accumulation's scale as Engine.denoise's.
+        Asynchronous, on the engine's stream after everything queued so far."""
+        self.check(lib().pt_denoise_variance(self.ctx, beauty.handle, normal_id.handle, albedo_weight.handle,
+                                             moments.handle, dst.handle, int(iterations), float(sigma_normal),
+                                             float(sigma_luminance), int(demodulate)), "pt_denoise_variance")
 
     def math_probe(self, op, x, y=None):
         x = np.ascontiguousarray(x, dtype=np.float32)
@@ -429,6 +441,13 @@ class Effect:
         self.engine.check(lib().pt_set_feature_targets(self.handle, normal_id.handle if normal_id is not None else None,
                                                        albedo_weight.handle if albedo_weight is not None else None),
                           "setFeatureTargets")
+
+    def setMomentTarget(self, moments=None):
+        """MI355X extension (pt_set_moment_target): while a render target is bound here, every draw of this
+        path-tracing effect also accumulates the luminance L of its radiance into it in place, by the beauty's
+        history rule - moments = (sum of L, sum of L^2, 0, weight). None unbinds it."""
+        self.engine.check(lib().pt_set_moment_target(self.handle, moments.handle if moments is not None else None),
+                          "setMomentTarget")
 
 
 class EffectWrapper:

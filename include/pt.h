@@ -277,6 +277,45 @@ int pt_set_feature_targets(pt_effect* fx, pt_texture* normal_id, pt_texture* alb
 int pt_denoise(pt_ctx* ctx, const pt_texture* beauty, const pt_texture* normal_id,
                const pt_texture* albedo_weight, pt_texture* dst,
                int iterations, float sigma_normal, float sigma_colour, int demodulate);
+/* Luminance moments: a third, independent feature target of a path-tracing effect (NULL unbinds it). `moments`
+ * is an RGBA32F render target of the draw target's size. While it is bound, every pt_render of the effect also
+ * folds the luminance of this draw's radiance r - CalculateRadiance's result, before the history rule and before
+ * the x 0.5 of a moving camera - into it in place, on the owned 16-row bands, with h and s as for
+ * pt_set_feature_targets above:
+ *   L = (0.2126 * r.x + 0.7152 * r.y) + 0.0722 * r.z
+ *   moments.x = h * old.x + s * L          moments.z = +0.0
+ *   moments.y = h * old.y + s * (L * L)    moments.w = h * old.w + s
+ * one IEEE binary32 operation per product and sum. So x / w and y / w are the first and second moment of the
+ * luminance over the samples the beauty holds, and y / w - (x / w)^2 its variance. The fold is the feature
+ * targets' (one launch, on the context's stream after the draw's own accumulation); with only this target bound a
+ * draw stages no G-buffer. The beauty, the canvas, every counter, pt_queue_stats and pt_cont_stats are bit for
+ * bit what they are without it. PT_ERR_ARG for a screenCopy / screenOutput effect or a texture that is not a
+ * render target of this context; pt_render returns PT_ERR_STATE when its size differs from the draw target's, or
+ * when it is the draw target, the bound previousBuffer or another bound feature target. Destroying the bound
+ * texture unbinds it. */
+int pt_set_moment_target(pt_effect* fx, pt_texture* moments);
+/* Variance-guided denoising: pt_denoise's a-trous filter with its colour edge-stop replaced by a luminance one
+ * that scales with each pixel's own variance (as in SVGF), so it blurs widely at 1 sample and lets go as the
+ * image converges. The five textures are RGBA32F render targets of `ctx` of one size; dst differs from the
+ * inputs. w, n, id, a, c, den = max(a, 1e-3) and d are pt_denoise's; mw = moments.w; lum(v) = (0.2126 v.x +
+ * 0.7152 v.y) + 0.0722 v.z. A pixel is valid when w > 0 and mw > 0; an invalid pixel writes (0, 0, 0, 1) and is
+ * skipped as a tap, like one outside the image or of another id.
+ * Variance: vt = moments.y / mw - (moments.x / mw)^2, and vs the same from the sums of moments.x, .y, .w over the
+ * kept taps of the 7x7 window; each 0 unless > 0. var = (mw < 4 ? vs : vt) / mw, the variance of the pixel's
+ * mean, divided by lum(den)^2 when demodulating.
+ * Pass i (spacing 2^i): gv = the mean of var over the kept taps of the 3x3 window at spacing 1 weighted {1/2, 1/4}
+ * per axis; each kept tap q of the 5x5 B3 kernel weighs K K exp(-(|n_p - n_q|^2 / sigma_normal^2 + (lum(d_p) -
+ * lum(d_q))^2 / (sigma_luminance^2 gv + 1e-8))); d' = sum wt d_q / sum wt, var' = sum wt^2 var_q / (sum wt)^2.
+ * sigma_luminance is not halved between passes. The output is pt_denoise's: remodulated, times w, dst.w = 1.
+ * Operation by operation: INTEGRATION.md "Denoising" and tests/denoise_var_ref.py.
+ * The contract is pt_denoise's: asynchronous on the context's stream, writes only dst, changes no statistic or
+ * timing window, filters the whole frame under a row partition. PT_ERR_ARG, before any device work: a bad handle,
+ * a texture of another context or not a render target, sizes that differ, dst equal to an input, iterations
+ * outside 1..5, a sigma that is not finite and > 0, demodulate other than 0 or 1. PT_ERR_UNSUPPORTED: a context of
+ * several parts. */
+int pt_denoise_variance(pt_ctx* ctx, const pt_texture* beauty, const pt_texture* normal_id,
+                        const pt_texture* albedo_weight, const pt_texture* moments, pt_texture* dst,
+                        int iterations, float sigma_normal, float sigma_luminance, int demodulate);
 /* Device self-test of the pinned GLSL built-ins (ops as the oracle's pto_math_probe). */
 int pt_math_probe(pt_ctx* ctx, int op, const float* x, const float* y, float* out, int n);
 /* Exhaustive device self-test of a fast built-in sequence against the IEEE operation it replaces,
