@@ -45,6 +45,7 @@
 #include "pt_dev.h"
 #include "pt_devmem.h"
 #include "pt_pairs.h"
+#include "pt_jpeg_enc.h"
 
 extern "C" {
 hipError_t pt_launch_exhaustive(int op, unsigned long long* bad, hipStream_t s);
@@ -58,6 +59,8 @@ hipError_t pt_launch_cont(int prog, const pt::TraceArgs* a, int waves, hipStream
 hipError_t pt_launch_output(const pt::OutputArgs* a, hipStream_t s, int waves);
 hipError_t pt_launch_denoise(const pt::DenoiseArgs* a, hipStream_t s);
 hipError_t pt_launch_denoise_var(const pt::DenoiseVarArgs* a, hipStream_t s);
+hipError_t pt_launch_jpeg_measure(const ptj::EncArgs* a, hipStream_t s);
+hipError_t pt_launch_jpeg_pack(const ptj::EncArgs* a, hipStream_t s);
 hipError_t pt_launch_math_probe(int op, const float* x, const float* y, float* out, int n, hipStream_t s);
 hipError_t pt_launch_persist(int prog, int count, const pt::TraceArgs* a, const pt::WfBufs* w, int tiles_x,
                              unsigned n_wave_tiles, unsigned per_wave, unsigned refill, hipStream_t s);
@@ -139,8 +142,9 @@ struct Dev {
     // pt::spill_slab), RAD rad[sets()], radiance + flag (pixels), FEAT feat[sets()][2], the G-buffer pt_trace stages
     // for pt_feature_fold, once a draw has feature targets bound (pixels), CONT pt_cont's records (records per
     // buffer set; pt::ContLayout), GB the persistent backend's G-buffer + radiance (pixels), DENOISE pt_denoise's
-    // three planes, colour[2] + guide (pixels), DENOISE_VAR pt_denoise_variance's, those and var[2] (pixels)
-    enum Slab { WF, LPT, SPILL, RAD, FEAT, CONT, GB, DENOISE, DENOISE_VAR, kSlabs };
+    // three planes, colour[2] + guide (pixels), DENOISE_VAR pt_denoise_variance's, those and var[2] (pixels), JPEG
+    // pt_canvas_encode_jpeg's workspace (bytes; pt::JpegLayout) and JPEG_OUT the stream it assembles (bytes)
+    enum Slab { WF, LPT, SPILL, RAD, FEAT, CONT, GB, DENOISE, DENOISE_VAR, JPEG, JPEG_OUT, kSlabs };
     DevMem slab[kSlabs];
     pt::WfBufs wf = {};
     size_t wf_pixels = 0, wf_spill = 0;
@@ -1659,6 +1663,57 @@ int dev_denoise_variance(Dev* c, const DevTex* beauty, const DevTex* normal_id, 
     a.var[0] = (float*)(a.guide + mem.size);
     a.var[1] = a.var[0] + mem.size;
     HIPCHK(c, pt_launch_denoise_var(&a, c->stream));
+    return PT_OK;
+}
+
+// pt_canvas_encode_jpeg: an observer of the canvas like dev_read_pixels. The length pass runs first (colour
+// conversion .. the scan of the row lengths); the host reads the stream's length, sizes the stream buffer from it,
+// and the last kernel assembles the stream, which is copied behind the header the host writes. No timing events,
+// no counters; the canvas is only read.
+int dev_canvas_encode_jpeg(Dev* c, int quality, uint8_t* dst, size_t capacity, size_t* size)
+{
+    if (!c) return PT_ERR_ARG;
+    if (!dst || !size) return fail(c, PT_ERR_ARG, "pt_canvas_encode_jpeg: dst and size must not be NULL");
+    if (quality < 1 || quality > 100) return fail(c, PT_ERR_ARG, "pt_canvas_encode_jpeg: quality must be 1..100");
+    if (!c->canvas || c->cw <= 0 || c->ch <= 0) return fail(c, PT_ERR_ARG, "pt_canvas_encode_jpeg: no canvas yet");
+    if (c->cw > 65535 || c->ch > 65535)   // (SOF0's 16-bit fields; the DRI field alone would allow 65535 x 8 columns)
+        return fail(c, PT_ERR_ARG, "pt_canvas_encode_jpeg: a JPEG is at most 65535 x 65535");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = flush_copy(c)) return rc;
+    const pt::JpegLayout L(c->cw, c->ch);
+    DevMem& mem = c->slab[Dev::JPEG];
+    if (L.bytes > mem.size)
+        if (int rc = mem.grow(c, L.bytes, L.bytes, WAIT_MAIN, false)) return rc;
+    ptj::EncArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.canvas = (const uint32_t*)c->canvas;
+    a.width = c->cw; a.height = c->ch;
+    a.mcus_x = (unsigned)(L.blocks_row / 3); a.rows = (unsigned)L.rows;
+    a.blocks_row = (unsigned)L.blocks_row; a.tiles = (unsigned)L.tiles;
+    a.row_stride = L.row_stride;
+    char* base = mem.as<char>();
+    a.coef = (int16_t*)(base + L.coef); a.bitoff = (uint32_t*)(base + L.bitoff);
+    a.bits = (uint32_t*)(base + L.bits); a.tileoff = (uint32_t*)(base + L.tileoff);
+    a.rowbits = (uint32_t*)(base + L.rowbits); a.rowlen = (uint32_t*)(base + L.rowlen);
+    a.rowoff = (unsigned long long*)(base + L.rowoff); a.total = (unsigned long long*)(base + L.total);
+    a.qt = ptj::quant_tables(quality);
+    HIPCHK(c, pt_launch_jpeg_measure(&a, c->stream));
+    unsigned long long stream = 0;
+    HIPCHK(c, hipMemcpyAsync(&stream, a.total, sizeof(stream), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (stream > L.stream_max()) return fail(c, PT_ERR_STATE, "pt_canvas_encode_jpeg: the stream's length is past its bound");
+    *size = pt::kJpegHeader + (size_t)stream;
+    if (capacity < *size) return fail(c, PT_ERR_ARG, "pt_canvas_encode_jpeg: destination too small");
+    DevMem& out = c->slab[Dev::JPEG_OUT];
+    if (stream > out.size) {   // with a quarter of headroom: the file of a converging canvas changes length every frame
+        const size_t room = pt::jpeg_out_room((size_t)stream, L.stream_max());
+        if (int rc = out.grow(c, room, room, WAIT_MAIN, false)) return rc;
+    }
+    a.out = out.as<uint8_t>();
+    HIPCHK(c, pt_launch_jpeg_pack(&a, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dst + pt::kJpegHeader, a.out, (size_t)stream, hipMemcpyDeviceToHost, c->stream));
+    ptj::write_header(dst, c->cw, c->ch, a.qt);   // (while the stream is on its way)
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return PT_OK;
 }
 

@@ -536,6 +536,14 @@ int pt_read_pixels(pt_ctx* c, const pt_texture* t, void* dst, size_t bytes)
     return pt_sync(c);
 }
 
+int pt_canvas_encode_jpeg(pt_ctx* c, int quality, uint8_t* dst, size_t capacity, size_t* size)
+{
+    if (!c) return PT_ERR_ARG;
+    if (c->n() > 1)   // the gathered canvas, as pt_read_pixels: every part's output and the gather first
+        if (int rc = pt_sync(c)) return rc;
+    return take(c, 0, dev_canvas_encode_jpeg(c->parts[0], quality, dst, capacity, size));
+}
+
 int pt_write_pixels(pt_ctx* c, pt_texture* t, const void* src, size_t bytes)
 {
     if (!c || !t) return PT_ERR_ARG;

@@ -1,0 +1,147 @@
+// pt_jpeg_enc.h — what the host and the kernels of pt_canvas_encode_jpeg share (pt_jpeg_enc.hip, pt_capi.cpp): the
+// Annex K tables of ITU-T T.81, the quantisation tables of a quality as libjpeg scales them, the Huffman codes
+// derived from the tables at compile time, the file header, and the kernels' argument block. Plain C++ over plain
+// numbers, no HIP. The format, stage by stage, is INTEGRATION.md "Encoding the canvas" and tests/jpeg_enc_ref.py.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+namespace ptj {
+
+constexpr uint8_t kZigzag[64] = {
+    0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
+    35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55,
+    62, 63 };
+
+// K.1, K.2: luminance and chrominance, natural order
+constexpr uint8_t kQBase[2][64] = {
+    { 16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56,
+      14, 17, 22, 29, 51, 87, 80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92,
+      49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99 },
+    { 17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99,
+      47, 66, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99,
+      99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99 } };
+
+// K.3 - K.6: codes per length 1..16, then the symbols in code order ([0] luminance, [1] chrominance)
+constexpr uint8_t kDcBits[2][16] = { { 0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0 },
+                                     { 0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0 } };
+constexpr uint8_t kDcVals[12] = { 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11 };
+constexpr uint8_t kAcBits[2][16] = { { 0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d },
+                                     { 0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77 } };
+constexpr uint8_t kAcVals[2][162] = {
+    { 0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71,
+      0x14, 0x32, 0x81, 0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72,
+      0x82, 0x09, 0x0a, 0x16, 0x17, 0x18, 0x19, 0x1a, 0x25, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37,
+      0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59,
+      0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x83,
+      0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3,
+      0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3,
+      0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2,
+      0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa },
+    { 0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22,
+      0x32, 0x81, 0x08, 0x14, 0x42, 0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1,
+      0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25, 0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36,
+      0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58,
+      0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a,
+      0x82, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a,
+      0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba,
+      0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda,
+      0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa } };
+
+// The canonical codes (Annex C) by symbol, code | length << 16; 0 for a symbol the table does not have.
+// dc[t][category 0..11], ac[t][run << 4 | category]: 0x00 is EOB, 0xF0 is ZRL.
+struct HuffCodes {
+    uint32_t dc[2][12];
+    uint32_t ac[2][256];
+};
+constexpr HuffCodes make_codes()
+{
+    HuffCodes h = {};
+    for (int t = 0; t < 2; t++) {
+        uint32_t code = 0;
+        int k = 0;
+        for (int len = 1; len <= 16; len++, code <<= 1)
+            for (int i = 0; i < kDcBits[t][len - 1]; i++) h.dc[t][kDcVals[k++]] = code++ | (uint32_t)len << 16;
+        code = 0;
+        k = 0;
+        for (int len = 1; len <= 16; len++, code <<= 1)
+            for (int i = 0; i < kAcBits[t][len - 1]; i++) h.ac[t][kAcVals[t][k++]] = code++ | (uint32_t)len << 16;
+    }
+    return h;
+}
+
+// the tables of `quality` 1..100 (jpeg_quality_scaling, baseline: entries 1..255), in zigzag order as DQT and
+// the kernels' lanes take them; [0] luminance, [1] chrominance
+struct QuantTables {
+    uint16_t q[2][64];
+};
+inline QuantTables quant_tables(int quality)
+{
+    const int s = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+    QuantTables t;
+    for (int i = 0; i < 2; i++)
+        for (int k = 0; k < 64; k++) {
+            const int v = (kQBase[i][kZigzag[k]] * s + 50) / 100;
+            t.q[i][k] = (uint16_t)(v < 1 ? 1 : v > 255 ? 255 : v);
+        }
+    return t;
+}
+
+// SOI, APP0 (JFIF 1.1, no density unit, 1x1), DQT 0 and 1, SOF0 (8-bit, three components of 1x1 sampling, tables
+// 0 1 1), DHT DC0 AC0 DC1 AC1, DRI (one MCU row), SOS: the bytes before the entropy-coded data. Returns their
+// count, which is pt::kJpegHeader for every size and quality.
+inline size_t write_header(uint8_t* dst, int width, int height, const QuantTables& qt)
+{
+    uint8_t* p = dst;
+    auto put = [&](int b) { *p++ = (uint8_t)b; };
+    auto put16 = [&](int v) { put(v >> 8); put(v & 255); };
+    auto seg = [&](int marker, int body) { put(0xFF); put(marker); put16(body + 2); };
+    put(0xFF); put(0xD8);
+    seg(0xE0, 14);
+    for (char ch : { 'J', 'F', 'I', 'F', '\0' }) put(ch);
+    put(1); put(1); put(0); put16(1); put16(1); put(0); put(0);
+    for (int i = 0; i < 2; i++) {
+        seg(0xDB, 65);
+        put(i);
+        for (int k = 0; k < 64; k++) put(qt.q[i][k]);
+    }
+    seg(0xC0, 15);
+    put(8); put16(height); put16(width); put(3);
+    for (int c = 0; c < 3; c++) { put(c + 1); put(0x11); put(c ? 1 : 0); }
+    for (int i = 0; i < 2; i++) {
+        seg(0xC4, 1 + 16 + 12);
+        put(0x00 | i);
+        for (int k = 0; k < 16; k++) put(kDcBits[i][k]);
+        for (int k = 0; k < 12; k++) put(kDcVals[k]);
+        seg(0xC4, 1 + 16 + 162);
+        put(0x10 | i);
+        for (int k = 0; k < 16; k++) put(kAcBits[i][k]);
+        for (int k = 0; k < 162; k++) put(kAcVals[i][k]);
+    }
+    seg(0xDD, 2);
+    put16((width + 7) / 8);
+    seg(0xDA, 10);
+    put(3); put(1); put(0x00); put(2); put(0x11); put(3); put(0x11); put(0); put(63); put(0);
+    return (size_t)(p - dst);
+}
+
+// the kernels' arguments: the canvas (RGBA8, rows bottom-up), the workspace arrays of pt::JpegLayout, and (for
+// the last kernel) the stream buffer
+struct EncArgs {
+    const uint32_t* canvas;
+    int width, height;
+    unsigned mcus_x, rows, blocks_row, tiles;
+    size_t row_stride;             // bytes of `bits` per row
+    int16_t* coef;
+    uint32_t* bitoff;
+    uint32_t* bits;
+    uint32_t* tileoff;
+    uint32_t* rowbits;
+    uint32_t* rowlen;
+    unsigned long long* rowoff;
+    unsigned long long* total;
+    uint8_t* out;
+    QuantTables qt;
+};
+
+}  // namespace ptj

@@ -159,6 +159,49 @@ constexpr size_t kSpillPerLane = kStackLevels - kStackLdsMin + 4;
 inline bool spill_fits(size_t lanes) { return lanes * kSpillPerLane <= 0xffffffffull; }
 inline size_t spill_slab(int p, size_t lanes) { return (size_t)p * lanes * kSpillPerLane; }
 
+// pt_canvas_encode_jpeg's workspace (pt_jpeg_enc.hip) for a canvas of mcus_x x rows 8x8 MCUs, three blocks (Y, Cb,
+// Cr) each; block b of a row is component b % 3 of MCU b / 3. Byte offsets: coef [blocks x 64 x 2 B] the quantised
+// coefficients in zigzag order | bitoff [blocks x 4 B] a block's AC bit count, then its first bit within its row |
+// bits [rows x row_stride] each row's entropy-coded bits before byte stuffing, MSB-first in big-endian 32-bit
+// words | tileoff [rows x tiles x 4 B] the 0xFF bytes before each kJpegTile-byte tile of a row | rowbits, rowlen,
+// rowoff [rows x 4 B, 4 B, 8 B] a row's bit count, its stuffed length with its marker, where it starts | total
+// [8 B] the stream's length.
+// A block's bits at most (kJpegBlockBytes): every coefficient codes in 4 bits less than 16 zeros and it would (a
+// ZRL is 11 bits, an EOB 4), so the longest block has 63 non-zero ACs of a 16-bit code and 10 value bits each and a
+// DC of an 11-bit code and 11 value bits, 1660 bits = 207.5 B; the quantiser clamps to those categories. The
+// stream: every byte of a row may be 0xFF and take a stuffed 0x00, and every row ends in a 2-byte RSTm or EOI.
+constexpr size_t kJpegBlockBytes = 208;
+constexpr size_t kJpegTile = 1024;      // bytes of a row one block of the stuffing kernels takes (256 lanes x 4 B)
+constexpr size_t kJpegHeader = 629;    // SOI .. SOS: what the host writes before the stream
+struct JpegLayout {
+    size_t blocks_row, rows, row_stride, tiles;
+    size_t coef, bitoff, bits, tileoff, rowbits, rowlen, rowoff, total, bytes;
+    JpegLayout(int width, int height)
+    {
+        blocks_row = 3 * (((size_t)width + 7) / 8);
+        rows = ((size_t)height + 7) / 8;
+        row_stride = blocks_row * kJpegBlockBytes;
+        tiles = (row_stride + kJpegTile - 1) / kJpegTile;
+        const size_t blocks = blocks_row * rows;
+        Carve c;
+        coef = c.take(blocks * 128); bitoff = c.take(blocks * 4);
+        bits = c.take(rows * row_stride);
+        tileoff = c.take(rows * tiles * 4);
+        rowbits = c.take(rows * 4); rowlen = c.take(rows * 4); rowoff = c.take(rows * 8);
+        total = c.take(8);
+        bytes = c.at;
+    }
+    // the stream's length at most: what no canvas of this size can exceed
+    size_t stream_max() const { return rows * (2 * row_stride + 2); }
+};
+// what the stream buffer grows to when a stream of `need` bytes does not fit: a quarter more, 64 KiB at least, and
+// never past the canvas's bound (so a call whose file is a little longer than the last one's does not reallocate)
+inline size_t jpeg_out_room(size_t need, size_t stream_max)
+{
+    const size_t want = need + need / 4 < 65536 ? 65536 : need + need / 4;
+    return want < stream_max ? want : stream_max;
+}
+
 // Frame overlap of the megakernel's draws (pt_capi.cpp, Dev): the sequencing state. Draw k = mk_seq takes buffer
 // set k % (depth + lag) and side stream k % depth, and its path tracing waits for the mark of draw
 // k - depth - lag + 1, or of the oldest draw after everything it must wait for (mark_floor).

@@ -23,6 +23,7 @@
 //   engine.denoise(beautyRT, normalRT, albedoRT, dstRT, opts) -> pt_denoise (extension: a-trous filter over them)
 //   effect.setMomentTarget(momentsRT)             -> pt_set_moment_target (extension: accumulated luminance moments)
 //   engine.denoiseVariance(beautyRT, normalRT, albedoRT, momentsRT, dstRT, opts) -> pt_denoise_variance
+//   engine.encodeCanvasJPEG(quality)              -> pt_canvas_encode_jpeg (extension: the canvas as a JPEG file)
 'use strict';
 const fs = require('fs');
 const path = require('path');
@@ -188,6 +189,20 @@ function install(BABYLON, opts) {
       const out = new Uint8Array(this.getRenderWidth() * this.getRenderHeight() * 4);
       check(this._pt, addon.pt_read_pixels(this._pt, null, out), 'readPixels');
       return out;
+    }
+    // MI355X extension (pt_canvas_encode_jpeg): the canvas as a baseline JPEG file (4:4:4, a restart interval per
+    // MCU row) encoded on the device, as a Buffer; the bytes are libjpeg-turbo's for the same pixels and quality.
+    // The buffer starts at the last call's length; the call is repeated once when it answers that it is too small.
+    encodeCanvasJPEG(quality = 90) {
+      let buf = Buffer.allocUnsafe(this._jpegCapacity || 65536);
+      let [rc, size] = addon.pt_canvas_encode_jpeg(this._pt, quality | 0, buf);
+      if (rc !== 0 && size > buf.length) {
+        buf = Buffer.allocUnsafe(size);
+        [rc, size] = addon.pt_canvas_encode_jpeg(this._pt, quality | 0, buf);
+      }
+      check(this._pt, rc, 'encodeCanvasJPEG');
+      this._jpegCapacity = Math.max(buf.length, size);
+      return buf.subarray(0, size);
     }
     // MI355X extension (pt_denoise): the edge-avoiding a-trous filter of the RenderTargetTexture `beauty`, guided
     // by the feature targets accumulated beside it (effect.setFeatureTargets), into `dst`: the accumulation's

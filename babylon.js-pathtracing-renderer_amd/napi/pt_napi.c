@@ -275,6 +275,19 @@ static napi_value ReadPixels(napi_env env, napi_callback_info info)
     if (!p) { napi_throw_type_error(env, NULL, "typed array expected"); return NULL; }
     return num(env, pt_read_pixels((pt_ctx*)handle(env, a[0]), (const pt_texture*)handle(env, a[1]), p, len));
 }
+/* pt_canvas_encode_jpeg(ctx, quality, out: Uint8Array) -> [status, size]: the file's length, or with PT_ERR_ARG
+ * the length `out` must have when it is too small */
+static napi_value CanvasEncodeJpeg(napi_env env, napi_callback_info info)
+{
+    napi_value a[MAXARGS], r; if (args(env, info, a, 3) < 0) return NULL;
+    size_t cap, size = 0; uint8_t* p = (uint8_t*)bytes_of(env, a[2], &cap);
+    if (!p) { napi_throw_type_error(env, NULL, "typed array expected"); return NULL; }
+    const int rc = pt_canvas_encode_jpeg((pt_ctx*)handle(env, a[0]), i32(env, a[1]), p, cap, &size);
+    CHECK(napi_create_array_with_length(env, 2, &r));
+    CHECK(napi_set_element(env, r, 0, num(env, rc)));
+    CHECK(napi_set_element(env, r, 1, num(env, (double)size)));
+    return r;
+}
 static napi_value WritePixels(napi_env env, napi_callback_info info)
 {
     napi_value a[MAXARGS]; if (args(env, info, a, 3) < 0) return NULL;
@@ -476,6 +489,7 @@ static napi_value Init(napi_env env, napi_value exports)
         { "pt_render_target_create", RtCreate }, { "pt_render_target_wrap", RtWrap },
         { "pt_render_target_resize", RtResize }, { "pt_texture_size", TexSize }, { "pt_texture_destroy", TexDestroy },
         { "pt_render", Render }, { "pt_read_pixels", ReadPixels }, { "pt_write_pixels", WritePixels },
+        { "pt_canvas_encode_jpeg", CanvasEncodeJpeg },
         { "pt_set_row_partition", RowPartition }, { "pt_set_backend", SetBackend }, { "pt_set_output_partition", SetOutputPartition }, { "pt_canvas_wrap", CanvasWrap }, { "pt_set_bvh_layout", SetBvhLayout },
         { "pt_bvh_layout_used", BvhLayoutUsed }, { "pt_set_stream", SetStream }, { "pt_texture_device_ptr", TexDevicePtr },
         { "pt_last_render_ms", LastRenderMs }, { "pt_timing_begin", TimingBegin }, { "pt_timing_end", TimingEnd },

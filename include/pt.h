@@ -144,6 +144,20 @@ int pt_render(pt_effect* fx, pt_texture* target);
 /* readPixels of a render target (RGBA32F, 16 B/texel) or of the canvas (tex NULL, RGBA8),
  * rows bottom-up; synchronises. */
 int pt_read_pixels(pt_ctx* ctx, const pt_texture* tex, void* dst, size_t bytes);
+/* MI355X extension (no reference counterpart: the page's canvas is the browser's). The canvas, as
+ * pt_read_pixels(ctx, NULL, ...) would return it now, encoded on the device as a baseline sequential JFIF file:
+ * 8-bit, three components, 4:4:4, the Annex K quantisation tables scaled by `quality` (1..100) and Huffman
+ * tables, one restart interval per row of 8x8 MCUs; scanline 0 is canvas row height - 1 and alpha is ignored.
+ * The bytes are those libjpeg-turbo writes for the same pixels and quality with 4:4:4 sampling and a restart
+ * marker per MCU row (stage by stage: INTEGRATION.md "Encoding the canvas", tests/jpeg_enc_ref.py).
+ * An observer like pt_read_pixels: a deferred screenCopy runs first, a context of several parts waits for the
+ * gather and encodes part 0's gathered canvas, a row or output partition encodes the canvas as it stands; it
+ * synchronises, and writes no texture, not the canvas, and no counter, statistic or timing window. Every stage
+ * runs on the context's stream in context-owned workspace; the host copies the stream's length and then that
+ * many bytes. *size receives the file's length. PT_ERR_ARG: capacity below that length (*size is then the
+ * length needed and nothing is written to dst), quality outside 1..100, NULL dst or size, no canvas yet, a canvas
+ * wider or taller than 65535 (the frame header's fields). */
+int pt_canvas_encode_jpeg(pt_ctx* ctx, int quality, uint8_t* dst, size_t capacity, size_t* size);
 /* Upload rows of a render target (RGBA32F), used to seed the history buffer in tests and to
  * land gathered bands on the root in multi-GPU runs. */
 int pt_write_pixels(pt_ctx* ctx, pt_texture* tex, const void* src, size_t bytes);
