@@ -1670,17 +1670,20 @@ int dev_denoise_variance(Dev* c, const DevTex* beauty, const DevTex* normal_id, 
 // conversion .. the scan of the row lengths); the host reads the stream's length, sizes the stream buffer from it,
 // and the last kernel assembles the stream, which is copied behind the header the host writes. No timing events,
 // no counters; the canvas is only read.
-int dev_canvas_encode_jpeg(Dev* c, int quality, uint8_t* dst, size_t capacity, size_t* size)
+int dev_canvas_encode_jpeg(Dev* c, int quality, int subsampling, uint8_t* dst, size_t capacity, size_t* size)
 {
     if (!c) return PT_ERR_ARG;
     if (!dst || !size) return fail(c, PT_ERR_ARG, "pt_canvas_encode_jpeg: dst and size must not be NULL");
     if (quality < 1 || quality > 100) return fail(c, PT_ERR_ARG, "pt_canvas_encode_jpeg: quality must be 1..100");
+    if (subsampling < PT_JPEG_444 || subsampling > PT_JPEG_420)
+        return fail(c, PT_ERR_ARG, "pt_canvas_encode_jpeg_sub: subsampling must be 0 (4:4:4), 1 (4:2:2) or 2 (4:2:0)");
     if (!c->canvas || c->cw <= 0 || c->ch <= 0) return fail(c, PT_ERR_ARG, "pt_canvas_encode_jpeg: no canvas yet");
     if (c->cw > 65535 || c->ch > 65535)   // (SOF0's 16-bit fields; the DRI field alone would allow 65535 x 8 columns)
         return fail(c, PT_ERR_ARG, "pt_canvas_encode_jpeg: a JPEG is at most 65535 x 65535");
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = flush_copy(c)) return rc;
-    const pt::JpegLayout L(c->cw, c->ch);
+    const int hs = ptj::sampling_h(subsampling), vs = ptj::sampling_v(subsampling);
+    const pt::JpegLayout L(c->cw, c->ch, hs, vs);
     DevMem& mem = c->slab[Dev::JPEG];
     if (L.bytes > mem.size)
         if (int rc = mem.grow(c, L.bytes, L.bytes, WAIT_MAIN, false)) return rc;
@@ -1688,7 +1691,8 @@ int dev_canvas_encode_jpeg(Dev* c, int quality, uint8_t* dst, size_t capacity, s
     std::memset(&a, 0, sizeof(a));
     a.canvas = (const uint32_t*)c->canvas;
     a.width = c->cw; a.height = c->ch;
-    a.mcus_x = (unsigned)(L.blocks_row / 3); a.rows = (unsigned)L.rows;
+    a.hs = hs; a.vs = vs;
+    a.mcus_x = (unsigned)L.mcus_x; a.rows = (unsigned)L.rows;
     a.blocks_row = (unsigned)L.blocks_row; a.tiles = (unsigned)L.tiles;
     a.row_stride = L.row_stride;
     char* base = mem.as<char>();
@@ -1712,7 +1716,7 @@ int dev_canvas_encode_jpeg(Dev* c, int quality, uint8_t* dst, size_t capacity, s
     a.out = out.as<uint8_t>();
     HIPCHK(c, pt_launch_jpeg_pack(&a, c->stream));
     HIPCHK(c, hipMemcpyAsync(dst + pt::kJpegHeader, a.out, (size_t)stream, hipMemcpyDeviceToHost, c->stream));
-    ptj::write_header(dst, c->cw, c->ch, a.qt);   // (while the stream is on its way)
+    ptj::write_header(dst, c->cw, c->ch, a.qt, hs, vs);   // (while the stream is on its way)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return PT_OK;
 }

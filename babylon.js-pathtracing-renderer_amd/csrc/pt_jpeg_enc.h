@@ -87,10 +87,10 @@ inline QuantTables quant_tables(int quality)
     return t;
 }
 
-// SOI, APP0 (JFIF 1.1, no density unit, 1x1), DQT 0 and 1, SOF0 (8-bit, three components of 1x1 sampling, tables
-// 0 1 1), DHT DC0 AC0 DC1 AC1, DRI (one MCU row), SOS: the bytes before the entropy-coded data. Returns their
-// count, which is pt::kJpegHeader for every size and quality.
-inline size_t write_header(uint8_t* dst, int width, int height, const QuantTables& qt)
+// SOI, APP0 (JFIF 1.1, no density unit, 1x1), DQT 0 and 1, SOF0 (8-bit, three components, Y sampled hs x vs and
+// Cb, Cr 1x1, tables 0 1 1), DHT DC0 AC0 DC1 AC1, DRI (one MCU row of 8 hs pixel wide MCUs), SOS: the bytes before
+// the entropy-coded data. Returns their count, which is pt::kJpegHeader for every size, quality and sampling.
+inline size_t write_header(uint8_t* dst, int width, int height, const QuantTables& qt, int hs = 1, int vs = 1)
 {
     uint8_t* p = dst;
     auto put = [&](int b) { *p++ = (uint8_t)b; };
@@ -107,7 +107,7 @@ inline size_t write_header(uint8_t* dst, int width, int height, const QuantTable
     }
     seg(0xC0, 15);
     put(8); put16(height); put16(width); put(3);
-    for (int c = 0; c < 3; c++) { put(c + 1); put(0x11); put(c ? 1 : 0); }
+    for (int c = 0; c < 3; c++) { put(c + 1); put(c ? 0x11 : hs << 4 | vs); put(c ? 1 : 0); }
     for (int i = 0; i < 2; i++) {
         seg(0xC4, 1 + 16 + 12);
         put(0x00 | i);
@@ -119,17 +119,22 @@ inline size_t write_header(uint8_t* dst, int width, int height, const QuantTable
         for (int k = 0; k < 162; k++) put(kAcVals[i][k]);
     }
     seg(0xDD, 2);
-    put16((width + 7) / 8);
+    put16((width + 8 * hs - 1) / (8 * hs));
     seg(0xDA, 10);
     put(3); put(1); put(0x00); put(2); put(0x11); put(3); put(0x11); put(0); put(63); put(0);
     return (size_t)(p - dst);
 }
 
-// the kernels' arguments: the canvas (RGBA8, rows bottom-up), the workspace arrays of pt::JpegLayout, and (for
-// the last kernel) the stream buffer
+// Y's sampling factors (Cb and Cr are 1 x 1) of a pt_jpeg_subsampling value 0..2: 4:4:4, 4:2:2, 4:2:0
+inline int sampling_h(int subsampling) { return subsampling ? 2 : 1; }
+inline int sampling_v(int subsampling) { return subsampling == 2 ? 2 : 1; }
+
+// the kernels' arguments: the canvas (RGBA8, rows bottom-up), Y's sampling (an MCU is 8 hs x 8 vs pixels and
+// hs vs + 2 blocks), the workspace arrays of pt::JpegLayout, and (for the last kernel) the stream buffer
 struct EncArgs {
     const uint32_t* canvas;
     int width, height;
+    int hs, vs;
     unsigned mcus_x, rows, blocks_row, tiles;
     size_t row_stride;             // bytes of `bits` per row
     int16_t* coef;

@@ -1,12 +1,16 @@
-// pt_jpeg_enc.hip — the canvas as a baseline JPEG, on the device (include/pt.h pt_canvas_encode_jpeg; the format,
-// stage by stage, is INTEGRATION.md "Encoding the canvas" and tests/jpeg_enc_ref.py). Integer arithmetic only, so
-// the bytes are libjpeg-turbo's. A wave is one 8x8 MCU and takes its three blocks (Y, Cb, Cr) in turn; lane k is
-// zigzag coefficient k. The workspace is pt::JpegLayout (pt_plan.h).
+// pt_jpeg_enc.hip — the canvas as a baseline JPEG, on the device (include/pt.h pt_canvas_encode_jpeg_sub; the
+// format, stage by stage, is INTEGRATION.md "Encoding the canvas" and tests/jpeg_enc_ref.py, jpeg_enc_sub_ref.py).
+// Integer arithmetic only, so the bytes are libjpeg-turbo's. A wave is one MCU of 8 hs x 8 vs pixels (Y sampled
+// hs x vs: 4:4:4 1x1, 4:2:2 2x1, 4:2:0 2x2) and takes its hs vs + 2 blocks (Y row-major, Cb, Cr) in turn; lane k is
+// zigzag coefficient k. The workspace is pt::JpegLayout (pt_plan.h). The first three kernels are instances per
+// sampling, so the 4:4:4 ones are the code they were before the other two.
 //
-//   pt_jpeg_dct          a wave per MCU: colour conversion with the edges repeated, jfdctint's two passes through
+//   pt_jpeg_dct          a wave per MCU: colour conversion with the edges repeated, Cb and Cr of a lane's hs x vs
+//                        pixels summed with jcsample's bias, jfdctint's two passes through
 //                        LDS (a lane computes its own output of the 8-point transform, the column pass at the
 //                        lane's zigzag position, so the zigzag costs nothing), quantisation; the coefficients as
-//                        int16 (128 B per block, one store per wave) and the block's AC bit count.
+//                        int16 (128 B per block, one store per wave) and the block's AC bit count. A Y block
+//                        outside the image (a dummy) is the DC of the block before it and no AC.
 //   pt_jpeg_scan_blocks  a block per MCU row: the DC category of every block against its predecessor, an exclusive
 //                        scan of the block lengths -> every block's first bit in its row and the row's bit count;
 //                        then it zeroes the words of the row's bit buffer that the row will use.
@@ -118,8 +122,29 @@ __device__ inline unsigned block_scan(unsigned v, unsigned* sh, unsigned& total)
     return base + inc - v;
 }
 
-__global__ __launch_bounds__(64 * kWaves) void pt_jpeg_dct(EncArgs a)
+// jccolor's fixed point, F(x) = int(x 65536 + 0.5), of an RGBA8 pixel
+__device__ inline int luma(uint32_t p)
 {
+    const int r = p & 255, g = p >> 8 & 255, b = p >> 16 & 255;
+    return (19595 * r + 38470 * g + 7471 * b + 32768) >> 16;
+}
+__device__ inline void chroma(uint32_t p, int& cb, int& cr)
+{
+    const int r = p & 255, g = p >> 8 & 255, b = p >> 16 & 255;
+    cb = (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16;
+    cr = (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16;
+}
+
+// How far back in its row the block at position j of an MCU of NY Y blocks finds the block its DC is predicted
+// from: a Y block the Y block before it, which for j = 0 is the last one of the MCU before (NY - 1 + 2 chroma
+// blocks back = 3 whatever NY), a chroma block its own component in the MCU before. The first MCU of a row has no
+// such block where that reaches past the row's start: the prediction is 0 there.
+template <int NY> __device__ inline unsigned dc_back(unsigned j) { return j >= NY ? NY + 2 : j ? 1 : 3; }
+
+// HS x VS is Y's sampling: the wave's MCU is 8 HS x 8 VS pixels, its blocks the VS rows of HS Y blocks, Cb, Cr.
+template <int HS, int VS> __global__ __launch_bounds__(64 * kWaves) void pt_jpeg_dct(EncArgs a)
+{
+    constexpr int NY = HS * VS;
     __shared__ int s_in[kWaves][64], s_mid[kWaves][64];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const size_t n_mcu = (size_t)a.mcus_x * a.rows;
@@ -128,44 +153,76 @@ __global__ __launch_bounds__(64 * kWaves) void pt_jpeg_dct(EncArgs a)
     if (!live) m = n_mcu - 1;
     const unsigned row = (unsigned)(m / a.mcus_x), mx = (unsigned)(m % a.mcus_x);
     const int x = lane & 7, y = lane >> 3;
-    const int px = min((int)mx * 8 + x, a.width - 1), py = min((int)row * 8 + y, a.height - 1);
-    const uint32_t p = a.canvas[(size_t)(a.height - 1 - py) * a.width + px];   // scanline 0 is the top canvas row
-    const int r = p & 255, g = p >> 8 & 255, b = p >> 16 & 255;
-    // jccolor's fixed point, F(x) = int(x 65536 + 0.5)
-    int s[3];
-    s[0] = (19595 * r + 38470 * g + 7471 * b + 32768) >> 16;
-    s[1] = (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16;
-    s[2] = (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16;
-    const int nat = kZigzag[lane], u = nat >> 3, v = nat & 7;
+    // scanline 0 is the top canvas row; the edges repeat
+    auto pixel = [&](int px, int py) {
+        return a.canvas[(size_t)(a.height - 1 - min(py, a.height - 1)) * a.width + min(px, a.width - 1)];
+    };
+    // every sample of the lane before the first barrier: s[0 .. NY) the Y blocks, s[NY] Cb, s[NY + 1] Cr
+    int s[NY + 2];
+    bool real[NY];   // (the same in every lane) a Y block outside the image's ceil(W / 8) x ceil(H / 8) is a dummy
 #pragma unroll
-    for (int c = 0; c < 3; c++) {
-        s_in[w][lane] = s[c] - 128;
+    for (int j = 0; j < NY; j++) {
+        const int bx = (int)mx * HS + j % HS, by = (int)row * VS + j / HS;
+        real[j] = NY == 1 || (bx < (a.width + 7) >> 3 && by < (a.height + 7) >> 3);   // (1x1: no MCU has one)
+        s[j] = real[j] ? luma(pixel(bx * 8 + x, by * 8 + y)) : 0;
+    }
+    {
+        // jcsample's h2v1 / h2v2 over the converted samples: the right edge repeats before the downsampling, the
+        // bottom edge up to a multiple of VS rows before it and in downsampled rows after it; the bias alternates
+        // with the output column (x's parity is the column's: an MCU starts at an even one)
+        const int cx = (int)mx * 8 + x, cy = min((int)row * 8 + y, (a.height + VS - 1) / VS - 1);
+        int cb = 0, cr = 0;
+#pragma unroll
+        for (int i = 0; i < NY; i++) {
+            int pb, pr;
+            chroma(pixel(cx * HS + i % HS, cy * VS + i / HS), pb, pr);
+            cb += pb;
+            cr += pr;
+        }
+        constexpr int sh = NY == 4 ? 2 : NY == 2 ? 1 : 0;
+        const int bias = NY == 4 ? 1 + (x & 1) : NY == 2 ? x & 1 : 0;
+        s[NY] = (cb + bias) >> sh;
+        s[NY + 1] = (cr + bias) >> sh;
+    }
+    const int nat = kZigzag[lane], u = nat >> 3, v = nat & 7;
+    int prev_dc = 0;   // the quantised DC of the block before, for a dummy
+#pragma unroll
+    for (int c = 0; c < NY + 2; c++) {
+        const bool is_real = c < NY ? real[c] : true;   // (a dummy keeps the barriers and skips the transform)
+        const int table = c < NY ? 0 : 1;
+        if (is_real) s_in[w][lane] = s[c] - 128;
         __syncthreads();
         int d[8];
-        for (int j = 0; j < 8; j++) d[j] = s_in[w][y * 8 + j];
-        s_mid[w][lane] = fdct8<true>(d, x);
+        if (is_real) {
+            for (int j = 0; j < 8; j++) d[j] = s_in[w][y * 8 + j];
+            s_mid[w][lane] = fdct8<true>(d, x);
+        }
         __syncthreads();
-        for (int j = 0; j < 8; j++) d[j] = s_mid[w][j * 8 + v];
-        const int f = fdct8<false>(d, u);
-        // jcdctmgr's quantiser: divide by 8 t, rounding half away from zero. The clamp never binds for 8-bit
-        // samples (|DC| <= 1024, |AC| <= 1020 at t = 1); it holds the block to the categories the tables have.
-        const int t8 = 8 * (int)a.qt.q[c ? 1 : 0][lane];
-        int q = (f < 0 ? -f : f) + (t8 >> 1);
-        q = q >= t8 ? q / t8 : 0;
-        q = f < 0 ? -min(q, lane ? 1023 : 1024) : min(q, 1023);
+        int q = lane ? 0 : prev_dc;
+        if (is_real) {
+            for (int j = 0; j < 8; j++) d[j] = s_mid[w][j * 8 + v];
+            const int f = fdct8<false>(d, u);
+            // jcdctmgr's quantiser: divide by 8 t, rounding half away from zero. The clamp never binds for 8-bit
+            // samples (|DC| <= 1024, |AC| <= 1020 at t = 1); it holds the block to the categories the tables have.
+            const int t8 = 8 * (int)a.qt.q[table][lane];
+            q = (f < 0 ? -f : f) + (t8 >> 1);
+            q = q >= t8 ? q / t8 : 0;
+            q = f < 0 ? -min(q, lane ? 1023 : 1024) : min(q, 1023);
+        }
+        if (c + 1 < NY) prev_dc = __shfl(q, 0);
         unsigned long long bits;
         int len;
-        lane_code(lane, q, 0, __ballot(q != 0), c ? 1 : 0, bits, len);
-        const int ac_bits = wave_sum(lane ? len : 0);
+        lane_code(lane, q, 0, __ballot(q != 0), table, bits, len);
+        const int ac_bits = wave_sum(lane ? len : 0);   // (a dummy's: the EOB)
         if (live) {
-            const size_t blk = (size_t)row * a.blocks_row + mx * 3 + c;
+            const size_t blk = (size_t)row * a.blocks_row + mx * (NY + 2) + c;
             a.coef[blk * 64 + lane] = (int16_t)q;
             if (lane == 0) a.bitoff[blk] = (uint32_t)ac_bits;
         }
     }
 }
 
-__global__ __launch_bounds__(256) void pt_jpeg_scan_blocks(EncArgs a)
+template <int NY> __global__ __launch_bounds__(256) void pt_jpeg_scan_blocks(EncArgs a)
 {
     __shared__ unsigned sh[4];
     const unsigned row = blockIdx.x;
@@ -175,9 +232,10 @@ __global__ __launch_bounds__(256) void pt_jpeg_scan_blocks(EncArgs a)
         const unsigned b = b0 + threadIdx.x;
         unsigned len = 0;
         if (b < a.blocks_row) {
-            const int dc = a.coef[(base + b) * 64], prev = b >= 3 ? a.coef[(base + b - 3) * 64] : 0;
+            const unsigned j = b % (NY + 2), back = dc_back<NY>(j);
+            const int dc = a.coef[(base + b) * 64], prev = b >= back ? a.coef[(base + b - back) * 64] : 0;
             const int d = dc - prev, n = 32 - __clz(d < 0 ? -d : d);
-            len = a.bitoff[base + b] + (kCodes.dc[b % 3 ? 1 : 0][n] >> 16) + n;
+            len = a.bitoff[base + b] + (kCodes.dc[j < NY ? 0 : 1][n] >> 16) + n;
         }
         unsigned total;
         const unsigned at = carry + block_scan(len, sh, total);
@@ -190,20 +248,21 @@ __global__ __launch_bounds__(256) void pt_jpeg_scan_blocks(EncArgs a)
     for (unsigned i = threadIdx.x; i < (carry + 127) / 128; i += 256) z[i] = make_uint4(0, 0, 0, 0);
 }
 
-__global__ __launch_bounds__(64 * kWaves) void pt_jpeg_emit(EncArgs a)
+template <int NY> __global__ __launch_bounds__(64 * kWaves) void pt_jpeg_emit(EncArgs a)
 {
     const int lane = threadIdx.x & 63;
     const size_t m = (size_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
     if (m >= (size_t)a.mcus_x * a.rows) return;   // (a whole wave: no block barrier below)
     const unsigned row = (unsigned)(m / a.mcus_x), mx = (unsigned)(m % a.mcus_x);
     uint32_t* words = (uint32_t*)((char*)a.bits + (size_t)row * a.row_stride);
-    for (int c = 0; c < 3; c++) {
-        const size_t blk = (size_t)row * a.blocks_row + mx * 3 + c;
+    for (int c = 0; c < NY + 2; c++) {
+        const size_t blk = (size_t)row * a.blocks_row + mx * (NY + 2) + c;
         const int v = a.coef[blk * 64 + lane];
-        const int prev = mx ? a.coef[(blk - 3) * 64] : 0;   // the prediction restarts with every row
+        const unsigned at_row = mx * (NY + 2) + c, back = dc_back<NY>((unsigned)c);
+        const int prev = at_row >= back ? a.coef[(blk - back) * 64] : 0;   // the prediction restarts with every row
         unsigned long long bits;
         int len;
-        lane_code(lane, v, prev, __ballot(v != 0), c ? 1 : 0, bits, len);
+        lane_code(lane, v, prev, __ballot(v != 0), c < NY ? 0 : 1, bits, len);
         const unsigned at = a.bitoff[blk] + (unsigned)(wave_scan(len, lane) - len);
         if (len) {
             // the lane's bits left-aligned in 64, then shifted to bit `at & 31` of a three-word window
@@ -259,7 +318,8 @@ __global__ __launch_bounds__(256) void pt_jpeg_scan_rows(EncArgs a)
     __shared__ unsigned sh[4];
     unsigned long long carry = 0;
     for (unsigned r0 = 0; r0 < a.rows; r0 += 256) {
-        // a tile of 256 rows in 32 bits: a row is below 2^24 bytes (65535 / 8 MCUs x 3 x 2 x 208 + 2)
+        // a tile of 256 rows in 32 bits: a row is below 2^24 bytes (4:4:4 65535 / 8 MCUs x 3 blocks x 2 x 208 + 2 =
+        // 10 223 618; 4:2:0 65535 / 16 MCUs x 6 x 2 x 208 + 2 the same, 4:2:2 x 4 x 2 x 208 + 2 = 6 815 746)
         const unsigned r = r0 + threadIdx.x, len = r < a.rows ? a.rowlen[r] : 0u;
         unsigned total;
         const unsigned at = block_scan(len, sh, total);
@@ -295,14 +355,23 @@ __global__ __launch_bounds__(256) void pt_jpeg_pack(EncArgs a)
 
 }  // namespace ptj
 
-// colour conversion .. the stream's length: what runs before the host can size the stream buffer
-extern "C" hipError_t pt_launch_jpeg_measure(const ptj::EncArgs* a, hipStream_t s)
+// the three kernels that know the MCU's blocks, at Y's sampling HS x VS
+template <int HS, int VS> static void launch_blocks(const ptj::EncArgs* a, hipStream_t s)
 {
     const size_t n_mcu = (size_t)a->mcus_x * a->rows;
     const dim3 mcus((unsigned)((n_mcu + ptj::kWaves - 1) / ptj::kWaves));
-    hipLaunchKernelGGL(ptj::pt_jpeg_dct, mcus, dim3(64 * ptj::kWaves), 0, s, *a);
-    hipLaunchKernelGGL(ptj::pt_jpeg_scan_blocks, dim3(a->rows), dim3(256), 0, s, *a);
-    hipLaunchKernelGGL(ptj::pt_jpeg_emit, mcus, dim3(64 * ptj::kWaves), 0, s, *a);
+    hipLaunchKernelGGL((ptj::pt_jpeg_dct<HS, VS>), mcus, dim3(64 * ptj::kWaves), 0, s, *a);
+    hipLaunchKernelGGL((ptj::pt_jpeg_scan_blocks<HS * VS>), dim3(a->rows), dim3(256), 0, s, *a);
+    hipLaunchKernelGGL((ptj::pt_jpeg_emit<HS * VS>), mcus, dim3(64 * ptj::kWaves), 0, s, *a);
+}
+
+// colour conversion .. the stream's length: what runs before the host can size the stream buffer
+extern "C" hipError_t pt_launch_jpeg_measure(const ptj::EncArgs* a, hipStream_t s)
+{
+    if (a->hs == 1 && a->vs == 1) launch_blocks<1, 1>(a, s);
+    else if (a->hs == 2 && a->vs == 1) launch_blocks<2, 1>(a, s);
+    else if (a->hs == 2 && a->vs == 2) launch_blocks<2, 2>(a, s);
+    else return hipErrorInvalidValue;   // (no kernel for any other sampling)
     hipLaunchKernelGGL(ptj::pt_jpeg_count_ff, dim3(a->rows), dim3(256), 0, s, *a);
     hipLaunchKernelGGL(ptj::pt_jpeg_scan_rows, dim3(1), dim3(256), 0, s, *a);
     return hipGetLastError();

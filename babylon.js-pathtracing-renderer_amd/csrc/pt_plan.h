@@ -159,13 +159,14 @@ constexpr size_t kSpillPerLane = kStackLevels - kStackLdsMin + 4;
 inline bool spill_fits(size_t lanes) { return lanes * kSpillPerLane <= 0xffffffffull; }
 inline size_t spill_slab(int p, size_t lanes) { return (size_t)p * lanes * kSpillPerLane; }
 
-// pt_canvas_encode_jpeg's workspace (pt_jpeg_enc.hip) for a canvas of mcus_x x rows 8x8 MCUs, three blocks (Y, Cb,
-// Cr) each; block b of a row is component b % 3 of MCU b / 3. Byte offsets: coef [blocks x 64 x 2 B] the quantised
-// coefficients in zigzag order | bitoff [blocks x 4 B] a block's AC bit count, then its first bit within its row |
-// bits [rows x row_stride] each row's entropy-coded bits before byte stuffing, MSB-first in big-endian 32-bit
-// words | tileoff [rows x tiles x 4 B] the 0xFF bytes before each kJpegTile-byte tile of a row | rowbits, rowlen,
-// rowoff [rows x 4 B, 4 B, 8 B] a row's bit count, its stuffed length with its marker, where it starts | total
-// [8 B] the stream's length.
+// pt_canvas_encode_jpeg_sub's workspace (pt_jpeg_enc.hip) for a canvas of mcus_x x rows MCUs of 8 hs x 8 vs pixels
+// (Y sampled hs x vs: 1x1, 2x1 or 2x2), hs vs + 2 blocks each in coded order: the vs rows of hs Y blocks, Cb, Cr;
+// block b of a row is position b % (hs vs + 2) of MCU b / (hs vs + 2). Byte offsets: coef [blocks x 64 x 2 B] the
+// quantised coefficients in zigzag order | bitoff [blocks x 4 B] a block's AC bit count, then its first bit within
+// its row | bits [rows x row_stride] each row's entropy-coded bits before byte stuffing, MSB-first in big-endian
+// 32-bit words | tileoff [rows x tiles x 4 B] the 0xFF bytes before each kJpegTile-byte tile of a row | rowbits,
+// rowlen, rowoff [rows x 4 B, 4 B, 8 B] a row's bit count, its stuffed length with its marker, where it starts |
+// total [8 B] the stream's length.
 // A block's bits at most (kJpegBlockBytes): every coefficient codes in 4 bits less than 16 zeros and it would (a
 // ZRL is 11 bits, an EOB 4), so the longest block has 63 non-zero ACs of a 16-bit code and 10 value bits each and a
 // DC of an 11-bit code and 11 value bits, 1660 bits = 207.5 B; the quantiser clamps to those categories. The
@@ -174,12 +175,13 @@ constexpr size_t kJpegBlockBytes = 208;
 constexpr size_t kJpegTile = 1024;      // bytes of a row one block of the stuffing kernels takes (256 lanes x 4 B)
 constexpr size_t kJpegHeader = 629;    // SOI .. SOS: what the host writes before the stream
 struct JpegLayout {
-    size_t blocks_row, rows, row_stride, tiles;
+    size_t mcus_x, blocks_row, rows, row_stride, tiles;
     size_t coef, bitoff, bits, tileoff, rowbits, rowlen, rowoff, total, bytes;
-    JpegLayout(int width, int height)
+    JpegLayout(int width, int height, int hs = 1, int vs = 1)
     {
-        blocks_row = 3 * (((size_t)width + 7) / 8);
-        rows = ((size_t)height + 7) / 8;
+        mcus_x = ((size_t)width + 8 * hs - 1) / (8 * hs);
+        blocks_row = mcus_x * (hs * vs + 2);
+        rows = ((size_t)height + 8 * vs - 1) / (8 * vs);
         row_stride = blocks_row * kJpegBlockBytes;
         tiles = (row_stride + kJpegTile - 1) / kJpegTile;
         const size_t blocks = blocks_row * rows;

@@ -158,6 +158,27 @@ int pt_read_pixels(pt_ctx* ctx, const pt_texture* tex, void* dst, size_t bytes);
  * length needed and nothing is written to dst), quality outside 1..100, NULL dst or size, no canvas yet, a canvas
  * wider or taller than 65535 (the frame header's fields). */
 int pt_canvas_encode_jpeg(pt_ctx* ctx, int quality, uint8_t* dst, size_t capacity, size_t* size);
+/* The same with chroma subsampling; pt_canvas_encode_jpeg(ctx, q, ...) is pt_canvas_encode_jpeg_sub(ctx, q,
+ * PT_JPEG_444, ...), and everything said there holds. Y is sampled hs x vs against Cb and Cr: 1x1 (4:4:4), 2x1
+ * (4:2:2) or 2x2 (4:2:0); the bytes are those libjpeg-turbo writes for the same pixels and quality with that
+ * subsampling and a restart marker per MCU row (tests/jpeg_enc_sub_ref.py). What the sampling changes:
+ *   header   SOF0's Y sampling byte is hs << 4 | vs; DRI holds the MCUs of a row, ceil(W / (8 hs)).
+ *   MCU      8 hs x 8 vs pixels; its blocks in coded order are the vs rows of hs Y blocks, then Cb, then Cr. One
+ *            restart interval per MCU row; each component's DC prediction runs over its blocks in coded order and
+ *            restarts at 0 with every MCU row.
+ *   Y        the sample of pixel (min(x, W-1), min(y, H-1)).
+ *   Cb, Cr   converted per full-resolution pixel (jccolor's fixed point), then downsampled as integers: the sample
+ *            at column cx, row cy reads the columns min(2cx, W-1) and min(2cx+1, W-1) of, with cy' = min(cy,
+ *            ceil(H / vs) - 1), the rows 2cy' and min(2cy'+1, H-1) (4:2:0) or the row cy' (4:2:2), and is
+ *            (a + b + c + d + 1 + (cx & 1)) >> 2 (4:2:0) or (a + b + (cx & 1)) >> 1 (4:2:2).
+ *   dummies  a Y block of an MCU outside the image's ceil(W / 8) x ceil(H / 8) blocks (W mod 16 in 1..8; for 4:2:0
+ *            also H mod 16 in 1..8) is not computed from pixels: 63 zero ACs and the quantised DC of the block
+ *            before it in the MCU, coded like any other block.
+ * The transform, quantiser, Huffman tables, bit order, padding, stuffing and markers are those of 4:4:4.
+ * PT_ERR_ARG also for a subsampling outside 0..2. */
+enum pt_jpeg_subsampling { PT_JPEG_444 = 0, PT_JPEG_422 = 1, PT_JPEG_420 = 2 };   /* Pillow's numbering */
+int pt_canvas_encode_jpeg_sub(pt_ctx* ctx, int quality, int subsampling,
+                              uint8_t* dst, size_t capacity, size_t* size);
 /* Upload rows of a render target (RGBA32F), used to seed the history buffer in tests and to
  * land gathered bands on the root in multi-GPU runs. */
 int pt_write_pixels(pt_ctx* ctx, pt_texture* tex, const void* src, size_t bytes);

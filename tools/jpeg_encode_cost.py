@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
-"""What pt_canvas_encode_jpeg costs: time per Engine.encode_canvas_jpeg call on the canvas of rendered dragon
-stand-in frames at 1920x1080 and 3840x2160, quality 75 and 90, with the file's size, beside its yardsticks
+"""What pt_canvas_encode_jpeg_sub costs: time per Engine.encode_canvas_jpeg call on the canvas of rendered dragon
+stand-in frames at 1920x1080 and 3840x2160, quality 75 and 90, at each --subsampling asked for (0 4:4:4, the
+default, 1 4:2:2, 2 4:2:0; the keys of the others are "q<quality>_s<subsampling>"), with the file's size, beside
+its yardsticks
 measured in the same run: pt_output on the same frames (its per-draw events in the engine's timing window), a
 pt_read_pixels of the same canvas (what a host that encodes on a CPU core must fetch first), and, where Pillow
 is installed, its one-thread encode of the same pixels with the same settings (the work the call replaces).
@@ -9,10 +11,11 @@ so it is timed two ways: `call_us` the host's clock around the call, and `stream
 around `reps` calls, both the least of `rounds` rounds. The split per kernel comes from a kernel trace of this
 program (rocprofv3 --kernel-trace --stats -- python tools/jpeg_encode_cost.py): the six pt_jpeg_* kernels.
 `bytes` is what the kernels move at least: the canvas read (4 B per pixel), the coefficients written and read
-(2 x 6 B per padded pixel) and the file; `kernel_bytes` the same per kernel and `kernel_floor_us` that at 8 TB/s.
+(2 x 128 B per block) and the file; `kernel_bytes` the same per kernel and `kernel_floor_us` that at 8 TB/s.
 Prints one JSON line.
 
-usage: jpeg_encode_cost.py [--sizes 1920x1080,3840x2160] [--qualities 75,90] [--frames 8] [--reps 20] [--rounds 3]"""
+usage: jpeg_encode_cost.py [--sizes 1920x1080,3840x2160] [--qualities 75,90] [--subsampling 0,1,2] [--frames 8]
+                           [--reps 20] [--rounds 3]"""
 import argparse
 import io
 import json
@@ -31,6 +34,7 @@ import helpers as H      # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--sizes", default="1920x1080,3840x2160")
 ap.add_argument("--qualities", default="75,90")
+ap.add_argument("--subsampling", default="0", help="0 4:4:4, 1 4:2:2, 2 4:2:0 (Pillow's numbering), comma-separated")
 ap.add_argument("--frames", type=int, default=8, help="still frames accumulated before the calls are timed")
 ap.add_argument("--reps", type=int, default=20)
 ap.add_argument("--rounds", type=int, default=3)
@@ -70,7 +74,7 @@ def output_us(e, p, output):
     return round(best, 1)
 
 
-def pillow_us(rgb, q):
+def pillow_us(rgb, q, ss):
     try:
         from PIL import Image
     except ImportError:
@@ -80,16 +84,23 @@ def pillow_us(rgb, q):
     for _ in range(3):
         buf = io.BytesIO()
         t0 = time.perf_counter()
-        img.save(buf, "JPEG", quality=q, subsampling=0, restart_marker_rows=1)
+        img.save(buf, "JPEG", quality=q, subsampling=ss, restart_marker_rows=1)
         us = (time.perf_counter() - t0) * 1e6
         best = us if best is None else min(best, us)
     return round(best, 1), buf.getvalue()
 
 
-def kernel_bytes(W, Hh, file_len):
+def block_counts(W, Hh, ss):
+    """(blocks, MCU rows): an MCU is 8 hs x 8 vs pixels and hs vs + 2 blocks"""
+    hs, vs = ((1, 1), (2, 1), (2, 2))[ss]
+    mcus_x, rows = -(-W // (8 * hs)), -(-Hh // (8 * vs))
+    return mcus_x * rows * (hs * vs + 2), rows
+
+
+def kernel_bytes(W, Hh, file_len, ss):
     """the bytes each kernel reads and writes at least: per block 128 B of coefficients and a 4 B
     offset, per MCU row three 4 B words and an 8 B offset, the bit buffer about the file's length (stream)"""
-    blocks, rows = 3 * ((W + 7) // 8) * ((Hh + 7) // 8), (Hh + 7) // 8
+    blocks, rows = block_counts(W, Hh, ss)
     stream = file_len - 629
     return {"pt_jpeg_dct": 4 * W * Hh + blocks * (128 + 4),            # canvas in; coefficients, AC bit counts out
             "pt_jpeg_scan_blocks": blocks * (2 + 4 + 4) + stream,      # a block's DC and count in, offset out; zeroes
@@ -119,20 +130,20 @@ for size in a.sizes.split(","):
     row["read_pixels_us"] = {"call": wall, "stream": dev, "bytes": 4 * W * Hh}
     canvas = e.read_canvas(W, Hh)
     rgb = canvas[::-1, :, :3].copy()
-    padded = ((W + 7) // 8 * 8) * ((Hh + 7) // 8 * 8)
-    for q in (int(v) for v in a.qualities.split(",")):
-        wall, dev = timed(lambda: e.encode_canvas_jpeg(q))
-        data = e.encode_canvas_jpeg(q)
-        moved = 4 * W * Hh + 12 * padded + len(data)
-        r = {"call_us": wall, "stream_us": dev, "file_bytes": len(data), "bytes": moved,
-             "byte_floor_us": round(moved / 8e12 * 1e6, 1), "kernel_bytes": kernel_bytes(W, Hh, len(data)),
-             "kernel_floor_us": {k: round(v / 8e12 * 1e6, 2) for k, v in kernel_bytes(W, Hh, len(data)).items()}}
-        pil = pillow_us(rgb, q)
+    for q, ss in ((int(v), int(s)) for v in a.qualities.split(",") for s in a.subsampling.split(",")):
+        wall, dev = timed(lambda: e.encode_canvas_jpeg(q, subsampling=ss))
+        data = e.encode_canvas_jpeg(q, subsampling=ss)
+        blocks = block_counts(W, Hh, ss)[0]
+        moved = 4 * W * Hh + 2 * 128 * blocks + len(data)
+        r = {"call_us": wall, "stream_us": dev, "file_bytes": len(data), "blocks": blocks, "bytes": moved,
+             "byte_floor_us": round(moved / 8e12 * 1e6, 1), "kernel_bytes": kernel_bytes(W, Hh, len(data), ss),
+             "kernel_floor_us": {k: round(v / 8e12 * 1e6, 2) for k, v in kernel_bytes(W, Hh, len(data), ss).items()}}
+        pil = pillow_us(rgb, q, ss)
         if pil is None:
             r["pillow_us"] = None   # Pillow is not installed here
         else:
             r["pillow_us"], r["same_bytes_as_pillow"] = pil[0], pil[1] == data
-        row["q%d" % q] = r
+        row["q%d" % q if ss == 0 else "q%d_s%d" % (q, ss)] = r
     out["sizes"]["%dx%d" % (W, Hh)] = row
     e.sync()
     e.set_stream(None)
