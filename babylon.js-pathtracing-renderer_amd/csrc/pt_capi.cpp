@@ -143,8 +143,9 @@ struct Dev {
     // for pt_feature_fold, once a draw has feature targets bound (pixels), CONT pt_cont's records (records per
     // buffer set; pt::ContLayout), GB the persistent backend's G-buffer + radiance (pixels), DENOISE pt_denoise's
     // three planes, colour[2] + guide (pixels), DENOISE_VAR pt_denoise_variance's, those and var[2] (pixels), JPEG
-    // pt_canvas_encode_jpeg's workspace (bytes; pt::JpegLayout) and JPEG_OUT the stream it assembles (bytes)
-    enum Slab { WF, LPT, SPILL, RAD, FEAT, CONT, GB, DENOISE, DENOISE_VAR, JPEG, JPEG_OUT, kSlabs };
+    // pt_canvas_encode_jpeg's workspace (bytes; pt::JpegLayout), JPEG_OUT the stream it assembles (bytes) and
+    // JPEG_OPT what optimised Huffman tables add (bytes; pt::JpegOptLayout)
+    enum Slab { WF, LPT, SPILL, RAD, FEAT, CONT, GB, DENOISE, DENOISE_VAR, JPEG, JPEG_OUT, JPEG_OPT, kSlabs };
     DevMem slab[kSlabs];
     pt::WfBufs wf = {};
     size_t wf_pixels = 0, wf_spill = 0;
@@ -1669,24 +1670,31 @@ int dev_denoise_variance(Dev* c, const DevTex* beauty, const DevTex* normal_id, 
 // pt_canvas_encode_jpeg: an observer of the canvas like dev_read_pixels. The length pass runs first (colour
 // conversion .. the scan of the row lengths); the host reads the stream's length, sizes the stream buffer from it,
 // and the last kernel assembles the stream, which is copied behind the header the host writes. No timing events,
-// no counters; the canvas is only read.
-int dev_canvas_encode_jpeg(Dev* c, int quality, int subsampling, uint8_t* dst, size_t capacity, size_t* size)
+// no counters; the canvas is only read. With `optimize` the length pass also counts the symbols and builds the
+// Huffman tables (the histograms are zeroed on the stream first), the tables come back with the stream's length in
+// the one copy, and the header, whose length they decide, is written from them.
+int dev_canvas_encode_jpeg(Dev* c, int quality, int subsampling, int optimize, uint8_t* dst, size_t capacity, size_t* size)
 {
     if (!c) return PT_ERR_ARG;
     if (!dst || !size) return fail(c, PT_ERR_ARG, "pt_canvas_encode_jpeg: dst and size must not be NULL");
     if (quality < 1 || quality > 100) return fail(c, PT_ERR_ARG, "pt_canvas_encode_jpeg: quality must be 1..100");
     if (subsampling < PT_JPEG_444 || subsampling > PT_JPEG_420)
         return fail(c, PT_ERR_ARG, "pt_canvas_encode_jpeg_sub: subsampling must be 0 (4:4:4), 1 (4:2:2) or 2 (4:2:0)");
+    if (optimize != 0 && optimize != 1) return fail(c, PT_ERR_ARG, "pt_canvas_encode_jpeg_opt: optimize must be 0 or 1");
     if (!c->canvas || c->cw <= 0 || c->ch <= 0) return fail(c, PT_ERR_ARG, "pt_canvas_encode_jpeg: no canvas yet");
     if (c->cw > 65535 || c->ch > 65535)   // (SOF0's 16-bit fields; the DRI field alone would allow 65535 x 8 columns)
         return fail(c, PT_ERR_ARG, "pt_canvas_encode_jpeg: a JPEG is at most 65535 x 65535");
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = flush_copy(c)) return rc;
     const int hs = ptj::sampling_h(subsampling), vs = ptj::sampling_v(subsampling);
-    const pt::JpegLayout L(c->cw, c->ch, hs, vs);
+    const pt::JpegLayout L(c->cw, c->ch, hs, vs, optimize ? pt::kJpegOptBlockBytes : pt::kJpegBlockBytes);
     DevMem& mem = c->slab[Dev::JPEG];
     if (L.bytes > mem.size)
         if (int rc = mem.grow(c, L.bytes, L.bytes, WAIT_MAIN, false)) return rc;
+    const pt::JpegOptLayout O;
+    DevMem& opt = c->slab[Dev::JPEG_OPT];
+    if (optimize && O.bytes > opt.size)
+        if (int rc = opt.grow(c, O.bytes, O.bytes, WAIT_MAIN, false)) return rc;
     ptj::EncArgs a;
     std::memset(&a, 0, sizeof(a));
     a.canvas = (const uint32_t*)c->canvas;
@@ -1701,12 +1709,31 @@ int dev_canvas_encode_jpeg(Dev* c, int quality, int subsampling, uint8_t* dst, s
     a.rowbits = (uint32_t*)(base + L.rowbits); a.rowlen = (uint32_t*)(base + L.rowlen);
     a.rowoff = (unsigned long long*)(base + L.rowoff); a.total = (unsigned long long*)(base + L.total);
     a.qt = ptj::quant_tables(quality);
+    struct {
+        unsigned long long stream;
+        ptj::OptTables tables;
+    } got = {};   // (JpegOptLayout: the tables right behind the length)
+    static_assert(sizeof(got) == 8 + pt::JpegOptLayout::kTables && sizeof(ptj::HuffCodes) == pt::JpegOptLayout::kCodes, "");
+    if (optimize) {
+        char* ob = opt.as<char>();
+        a.hist = (unsigned long long*)(ob + O.hist); a.codes = (ptj::HuffCodes*)(ob + O.codes);
+        a.total = (unsigned long long*)(ob + O.total); a.tables = (ptj::OptTables*)(ob + O.tables);
+        HIPCHK(c, hipMemsetAsync(a.hist, 0, pt::JpegOptLayout::kHist, c->stream));
+    }
     HIPCHK(c, pt_launch_jpeg_measure(&a, c->stream));
-    unsigned long long stream = 0;
-    HIPCHK(c, hipMemcpyAsync(&stream, a.total, sizeof(stream), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&got, a.total, optimize ? sizeof(got) : sizeof(got.stream), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    const unsigned long long stream = got.stream;
     if (stream > L.stream_max()) return fail(c, PT_ERR_STATE, "pt_canvas_encode_jpeg: the stream's length is past its bound");
-    *size = pt::kJpegHeader + (size_t)stream;
+    uint8_t head[ptj::kOptHeaderMax];
+    size_t header = pt::kJpegHeader;
+    if (optimize) {
+        for (int t = 0; t < 4; t++)
+            if (ptj::opt_table_symbols(got.tables, t) < 1)
+                return fail(c, PT_ERR_STATE, "pt_canvas_encode_jpeg_opt: the device built no Huffman table");
+        header = ptj::write_header(head, c->cw, c->ch, a.qt, hs, vs, got.tables);
+    }
+    *size = header + (size_t)stream;
     if (capacity < *size) return fail(c, PT_ERR_ARG, "pt_canvas_encode_jpeg: destination too small");
     DevMem& out = c->slab[Dev::JPEG_OUT];
     if (stream > out.size) {   // with a quarter of headroom: the file of a converging canvas changes length every frame
@@ -1715,8 +1742,9 @@ int dev_canvas_encode_jpeg(Dev* c, int quality, int subsampling, uint8_t* dst, s
     }
     a.out = out.as<uint8_t>();
     HIPCHK(c, pt_launch_jpeg_pack(&a, c->stream));
-    HIPCHK(c, hipMemcpyAsync(dst + pt::kJpegHeader, a.out, (size_t)stream, hipMemcpyDeviceToHost, c->stream));
-    ptj::write_header(dst, c->cw, c->ch, a.qt, hs, vs);   // (while the stream is on its way)
+    HIPCHK(c, hipMemcpyAsync(dst + header, a.out, (size_t)stream, hipMemcpyDeviceToHost, c->stream));
+    if (optimize) std::memcpy(dst, head, header);
+    else ptj::write_header(dst, c->cw, c->ch, a.qt, hs, vs);   // (while the stream is on its way)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return PT_OK;
 }

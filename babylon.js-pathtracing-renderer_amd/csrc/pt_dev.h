@@ -71,7 +71,7 @@ int dev_set_moment_target(DevFx* fx, DevTex* moments);
 int dev_denoise_variance(Dev* c, const DevTex* beauty, const DevTex* normal_id, const DevTex* albedo_weight,
                          const DevTex* moments, DevTex* dst, int iterations, float sigma_normal, float sigma_luminance,
                          int demodulate);
-int dev_canvas_encode_jpeg(Dev* c, int quality, int subsampling, uint8_t* dst, size_t capacity, size_t* size);
+int dev_canvas_encode_jpeg(Dev* c, int quality, int subsampling, int optimize, uint8_t* dst, size_t capacity, size_t* size);
 int dev_math_exhaustive(Dev* c, int op, uint64_t* mismatches);
 int dev_math_probe(Dev* c, int op, const float* x, const float* y, float* out, int n);
 

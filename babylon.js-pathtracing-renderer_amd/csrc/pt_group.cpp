@@ -536,14 +536,21 @@ int pt_read_pixels(pt_ctx* c, const pt_texture* t, void* dst, size_t bytes)
     return pt_sync(c);
 }
 
-int pt_canvas_encode_jpeg_sub(pt_ctx* c, int quality, int subsampling, uint8_t* dst, size_t capacity, size_t* size)
+int pt_canvas_encode_jpeg_opt(pt_ctx* c, int quality, int subsampling, int optimize, uint8_t* dst, size_t capacity,
+                              size_t* size)
 {
     if (!c) return PT_ERR_ARG;
     if (subsampling < PT_JPEG_444 || subsampling > PT_JPEG_420)   // (before the parts are made to wait)
         return fail(c, PT_ERR_ARG, "pt_canvas_encode_jpeg_sub: subsampling must be 0 (4:4:4), 1 (4:2:2) or 2 (4:2:0)");
+    if (optimize != 0 && optimize != 1) return fail(c, PT_ERR_ARG, "pt_canvas_encode_jpeg_opt: optimize must be 0 or 1");
     if (c->n() > 1)   // the gathered canvas, as pt_read_pixels: every part's output and the gather first
         if (int rc = pt_sync(c)) return rc;
-    return take(c, 0, dev_canvas_encode_jpeg(c->parts[0], quality, subsampling, dst, capacity, size));
+    return take(c, 0, dev_canvas_encode_jpeg(c->parts[0], quality, subsampling, optimize, dst, capacity, size));
+}
+
+int pt_canvas_encode_jpeg_sub(pt_ctx* c, int quality, int subsampling, uint8_t* dst, size_t capacity, size_t* size)
+{
+    return pt_canvas_encode_jpeg_opt(c, quality, subsampling, 0, dst, capacity, size);
 }
 
 int pt_canvas_encode_jpeg(pt_ctx* c, int quality, uint8_t* dst, size_t capacity, size_t* size)

@@ -1,7 +1,8 @@
 // pt_jpeg_enc.h — what the host and the kernels of pt_canvas_encode_jpeg share (pt_jpeg_enc.hip, pt_capi.cpp): the
 // Annex K tables of ITU-T T.81, the quantisation tables of a quality as libjpeg scales them, the Huffman codes
-// derived from the tables at compile time, the file header, and the kernels' argument block. Plain C++ over plain
-// numbers, no HIP. The format, stage by stage, is INTEGRATION.md "Encoding the canvas" and tests/jpeg_enc_ref.py.
+// derived from the tables at compile time, the file header, a lane's symbols and bits under tables built for the
+// frame (optimised coding), and the kernels' argument block. Plain C++ over plain numbers, no HIP. The format, stage
+// by stage, is INTEGRATION.md "Encoding the canvas" and tests/jpeg_enc_ref.py, jpeg_enc_sub_ref.py, jpeg_enc_opt_ref.py.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -87,10 +88,31 @@ inline QuantTables quant_tables(int quality)
     return t;
 }
 
+// The four Huffman tables of a file coded with tables of its own (pt_canvas_encode_jpeg_opt with optimize = 1), as
+// DHT carries them, in the header's order DC 0, AC 0, DC 1, AC 1: codes per length 1..16, then the symbols by length
+// and value (sum of bits[t] of them). pt_jpeg_build_tables writes it, the host reads it back.
+struct OptTables {
+    uint8_t bits[4][16];
+    uint8_t vals[4][256];
+};
+// the symbols of table t, or -1 where it is no table of this encoder (more than 256 symbols; a DC category past 11)
+inline int opt_table_symbols(const OptTables& o, int t)
+{
+    int n = 0;
+    for (int k = 0; k < 16; k++) n += o.bits[t][k];
+    if (n > 256) return -1;
+    if (!(t & 1))
+        for (int i = 0; i < n; i++)
+            if (o.vals[t][i] > 11) return -1;
+    return n;
+}
+
 // SOI, APP0 (JFIF 1.1, no density unit, 1x1), DQT 0 and 1, SOF0 (8-bit, three components, Y sampled hs x vs and
 // Cb, Cr 1x1, tables 0 1 1), DHT DC0 AC0 DC1 AC1, DRI (one MCU row of 8 hs pixel wide MCUs), SOS: the bytes before
-// the entropy-coded data. Returns their count, which is pt::kJpegHeader for every size, quality and sampling.
-inline size_t write_header(uint8_t* dst, int width, int height, const QuantTables& qt, int hs = 1, int vs = 1)
+// the entropy-coded data. Returns their count, which is pt::kJpegHeader for every size, quality and sampling with
+// the Annex K tables (o == nullptr); with the tables of `o` the DHT segments carry those and the count varies.
+inline size_t write_header_tables(uint8_t* dst, int width, int height, const QuantTables& qt, int hs, int vs,
+                                  const OptTables* o)
 {
     uint8_t* p = dst;
     auto put = [&](int b) { *p++ = (uint8_t)b; };
@@ -108,7 +130,14 @@ inline size_t write_header(uint8_t* dst, int width, int height, const QuantTable
     seg(0xC0, 15);
     put(8); put16(height); put16(width); put(3);
     for (int c = 0; c < 3; c++) { put(c + 1); put(c ? 0x11 : hs << 4 | vs); put(c ? 1 : 0); }
-    for (int i = 0; i < 2; i++) {
+    for (int t = 0; o && t < 4; t++) {
+        const int syms = opt_table_symbols(*o, t);
+        seg(0xC4, 1 + 16 + syms);
+        put((t & 1) << 4 | t >> 1);
+        for (int k = 0; k < 16; k++) put(o->bits[t][k]);
+        for (int k = 0; k < syms; k++) put(o->vals[t][k]);
+    }
+    for (int i = 0; !o && i < 2; i++) {
         seg(0xC4, 1 + 16 + 12);
         put(0x00 | i);
         for (int k = 0; k < 16; k++) put(kDcBits[i][k]);
@@ -123,6 +152,97 @@ inline size_t write_header(uint8_t* dst, int width, int height, const QuantTable
     seg(0xDA, 10);
     put(3); put(1); put(0x00); put(2); put(0x11); put(3); put(0x11); put(0); put(63); put(0);
     return (size_t)(p - dst);
+}
+inline size_t write_header(uint8_t* dst, int width, int height, const QuantTables& qt, int hs = 1, int vs = 1)
+{
+    return write_header_tables(dst, width, height, qt, hs, vs, nullptr);
+}
+
+// ---- optimised Huffman tables (pt_canvas_encode_jpeg_opt with optimize = 1; tests/jpeg_enc_opt_ref.py) ----
+#if defined(__HIPCC__)
+#define PTJ_HD __host__ __device__
+#else
+#define PTJ_HD
+#endif
+
+PTJ_HD inline int bit_width(unsigned a) { return a ? 32 - __builtin_clz(a) : 0; }
+
+// Lane k's symbols of a block (libjpeg's htest_one_block, a coefficient a lane): v the lane's coefficient, prev_dc
+// the DC the block is predicted from, `nonzero` the mask of lanes holding a non-zero coefficient. sym: the DC
+// category for k = 0, (run & 15) << 4 | size for a non-zero AC after `run` zeros, 0x00 (EOB) for lane 63 holding a
+// zero, -1 for no symbol; zrls: the run >> 4 ZRL symbols (0xF0) before an AC's own; n, val: the value bits.
+struct LaneSyms {
+    int sym, zrls, n;
+    uint32_t val;
+};
+PTJ_HD inline LaneSyms lane_symbols(int k, int v, int prev_dc, unsigned long long nonzero)
+{
+    LaneSyms s = { -1, 0, 0, 0 };
+    if (k == 0) {
+        const int d = v - prev_dc;
+        s.n = bit_width((unsigned)(d < 0 ? -d : d));
+        s.sym = s.n;
+        s.val = (uint32_t)(d < 0 ? d - 1 : d) & ((1u << s.n) - 1u);
+    } else if (v != 0) {
+        const unsigned long long below = nonzero & ((1ull << k) - 1ull) & ~1ull;
+        const int run = k - 1 - (below ? 63 - __builtin_clzll(below) : 0);
+        s.n = bit_width((unsigned)(v < 0 ? -v : v));
+        s.zrls = run >> 4;
+        s.sym = (run & 15) << 4 | s.n;
+        s.val = (uint32_t)(v < 0 ? v - 1 : v) & ((1u << s.n) - 1u);
+    } else if (k == 63) {
+        s.sym = 0x00;
+    }
+    return s;
+}
+
+// A lane's share of a block's bits under tables of any code lengths up to 16: the ZRLs (at most 3 x 16 bits) apart
+// from the code and value (at most 16 + 11), each right-aligned; 74 bits in all at most, which no 64-bit word holds.
+struct LaneBits {
+    unsigned long long zrl;
+    uint32_t code;
+    int zrl_len, code_len;
+};
+PTJ_HD inline LaneBits lane_bits(const LaneSyms& s, const uint32_t* table, uint32_t zrl)
+{
+    LaneBits b = { 0, 0, 0, 0 };
+    if (s.sym < 0) return b;
+    for (int i = 0; i < s.zrls; i++) {
+        b.zrl = b.zrl << (zrl >> 16) | (zrl & 0xFFFFu);
+        b.zrl_len += (int)(zrl >> 16);
+    }
+    const uint32_t e = table[s.sym];
+    b.code = (e & 0xFFFFu) << s.n | s.val;
+    b.code_len = (int)(e >> 16) + s.n;
+    return b;
+}
+// ... and where it goes: the share starts at bit `at` of a buffer that is MSB-first in 32-bit words; w[0..3] are
+// the words at at >> 5 and after with the share's bits in place and zeros elsewhere (31 + 74 bits <= 4 words)
+PTJ_HD inline void lane_window(const LaneBits& b, unsigned at, uint32_t w[4])
+{
+    unsigned long long hi = 0, lo = 0;   // the window's first and second 64 bits
+    auto place = [&](unsigned long long bits, int len, unsigned pos) {   // len 1..64 right-aligned bits to bit pos < 96
+        const unsigned long long left = bits << (64 - len);
+        if (pos < 64) {
+            hi |= left >> pos;
+            if (pos) lo |= left << (64 - pos);
+        } else {
+            lo |= left >> (pos - 64);
+        }
+    };
+    const unsigned sh = at & 31;
+    if (b.zrl_len) place(b.zrl, b.zrl_len, sh);
+    if (b.code_len) place(b.code, b.code_len, sh + (unsigned)b.zrl_len);
+    w[0] = (uint32_t)(hi >> 32); w[1] = (uint32_t)hi;
+    w[2] = (uint32_t)(lo >> 32); w[3] = (uint32_t)lo;
+}
+
+// The header with the four DHT segments carrying `o` instead of Annex K: the same segments in the same order, its
+// length what the tables' symbols make it (at most kOptHeaderMax). Every table of `o` must pass opt_table_symbols.
+constexpr size_t kOptHeaderMax = 629 - 2 * (12 + 162) + 4 * 256;
+inline size_t write_header(uint8_t* dst, int width, int height, const QuantTables& qt, int hs, int vs, const OptTables& o)
+{
+    return write_header_tables(dst, width, height, qt, hs, vs, &o);
 }
 
 // Y's sampling factors (Cb and Cr are 1 x 1) of a pt_jpeg_subsampling value 0..2: 4:4:4, 4:2:2, 4:2:0
@@ -147,6 +267,10 @@ struct EncArgs {
     unsigned long long* total;
     uint8_t* out;
     QuantTables qt;
+    // optimised tables only (pt::JpegOptLayout; all nullptr with the Annex K tables)
+    unsigned long long* hist;      // [4][256] symbol counts: DC 0, AC 0, DC 1, AC 1
+    HuffCodes* codes;              // the codes pt_jpeg_build_tables derives
+    OptTables* tables;             // ... and the tables for the header, behind `total`
 };
 
 }  // namespace ptj

@@ -1,4 +1,4 @@
-// pt_jpeg_enc.hip — the canvas as a baseline JPEG, on the device (include/pt.h pt_canvas_encode_jpeg_sub; the
+// pt_jpeg_enc.hip — the canvas as a baseline JPEG, on the device (include/pt.h pt_canvas_encode_jpeg_opt; the
 // format, stage by stage, is INTEGRATION.md "Encoding the canvas" and tests/jpeg_enc_ref.py, jpeg_enc_sub_ref.py).
 // Integer arithmetic only, so the bytes are libjpeg-turbo's. A wave is one MCU of 8 hs x 8 vs pixels (Y sampled
 // hs x vs: 4:4:4 1x1, 4:2:2 2x1, 4:2:0 2x2) and takes its hs vs + 2 blocks (Y row-major, Cb, Cr) in turn; lane k is
@@ -22,9 +22,16 @@
 //   pt_jpeg_scan_rows    one block: the exclusive scan of the row lengths, and the stream's length.
 //   pt_jpeg_pack         a block per tile: every byte to its place in the stream, a 0x00 after every 0xFF, RSTm
 //                        after every row but the last and EOI after that one.
-// No kernel writes outside the workspace whatever the pixels: a block's bits are bounded by kJpegBlockBytes
-// (pt_plan.h) because the quantiser clamps to the categories the tables have, and the stream buffer is allocated
-// from the length pt_jpeg_scan_rows computed.
+// With optimised tables (pt_canvas_encode_jpeg_opt, optimize = 1; tests/jpeg_enc_opt_ref.py) three kernels run
+// between pt_jpeg_dct and pt_jpeg_scan_blocks, and that one and pt_jpeg_emit are their OPT instances, which read
+// the tables built on the device (pt::JpegOptLayout) where the others read the Annex K codes:
+//   pt_jpeg_hist         a wave per MCU: the symbols the emitter will write, counted per table in LDS and then in
+//                        the four global histograms.
+//   pt_jpeg_build_tables a wave per table: libjpeg's jpeg_gen_optimal_table, the tables for the header and the codes.
+//   pt_jpeg_block_bits   a wave per MCU: every block's AC bit count again, under those codes.
+// No kernel writes outside the workspace whatever the pixels: a block's bits are bounded by kJpegBlockBytes, or
+// kJpegOptBlockBytes under tables of any code lengths up to 16 (pt_plan.h), because the quantiser clamps to the
+// categories the tables have, and the stream buffer is allocated from the length pt_jpeg_scan_rows computed.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -222,7 +229,195 @@ template <int HS, int VS> __global__ __launch_bounds__(64 * kWaves) void pt_jpeg
     }
 }
 
-template <int NY> __global__ __launch_bounds__(256) void pt_jpeg_scan_blocks(EncArgs a)
+// ---- optimised tables: the statistics, the tables, and every block's AC bit count under them ----
+
+// Block c of MCU mx of `row`: lane k's coefficient and the DC the block is predicted from (0 at the row's start)
+template <int NY> __device__ inline void load_block(const EncArgs& a, unsigned row, unsigned mx, int c, int lane,
+                                                     size_t& blk, int& v, int& prev)
+{
+    blk = (size_t)row * a.blocks_row + mx * (NY + 2) + c;
+    v = a.coef[blk * 64 + lane];
+    const unsigned at_row = mx * (NY + 2) + c, back = dc_back<NY>((unsigned)c);
+    prev = at_row >= back ? a.coef[(blk - back) * 64] : 0;
+}
+// lane k's bits under the tables pt_jpeg_build_tables derived
+__device__ inline LaneBits lane_code_opt(const HuffCodes* codes, int k, int v, int prev, unsigned long long nonzero, int table)
+{
+    return lane_bits(lane_symbols(k, v, prev, nonzero), k ? codes->ac[table] : codes->dc[table], codes->ac[table][0xF0]);
+}
+
+constexpr unsigned kHistBlocks = 1024;   // pt_jpeg_hist's grid at most: each block adds its counts to the global ones once
+
+// A wave per MCU, MCUs in a grid-stride loop: the symbols the emitter will write (libjpeg's htest_one_block), counted
+// in LDS and added to a.hist once per block. Integer counts: the result does not depend on the order. A block's LDS
+// counter stays in 32 bits: at most 2^26 MCUs x 6 blocks x 63 symbols / kHistBlocks.
+template <int NY> __global__ __launch_bounds__(64 * kWaves) void pt_jpeg_hist(EncArgs a)
+{
+    __shared__ unsigned s_hist[4 * 256];
+    for (unsigned i = threadIdx.x; i < 4 * 256; i += 64 * kWaves) s_hist[i] = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const size_t n_mcu = (size_t)a.mcus_x * a.rows;
+    for (size_t m = (size_t)blockIdx.x * kWaves + (threadIdx.x >> 6); m < n_mcu; m += (size_t)gridDim.x * kWaves) {
+        const unsigned row = (unsigned)(m / a.mcus_x), mx = (unsigned)(m % a.mcus_x);
+        for (int c = 0; c < NY + 2; c++) {
+            size_t blk;
+            int v, prev;
+            load_block<NY>(a, row, mx, c, lane, blk, v, prev);
+            const LaneSyms s = lane_symbols(lane, v, prev, __ballot(v != 0));
+            unsigned* h = s_hist + ((c < NY ? 0 : 2) + (lane ? 1 : 0)) * 256;   // (a DC category is at most 11)
+            if (s.sym >= 0) atomicAdd(h + s.sym, 1u);
+            if (s.zrls) atomicAdd(h + 0xF0, (unsigned)s.zrls);
+        }
+    }
+    __syncthreads();
+    for (unsigned i = threadIdx.x; i < 4 * 256; i += 64 * kWaves)
+        if (const unsigned n = s_hist[i]) atomicAdd(a.hist + i, (unsigned long long)n);
+}
+
+// the wave's two least of every lane's a <= b, in every lane (the keys differ but for the "none" key)
+__device__ inline void wave_min2(unsigned long long& a, unsigned long long& b)
+{
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long c = __shfl_xor(a, o), d = __shfl_xor(b, o);
+        const unsigned long long hi = a < c ? c : a, next = b < d ? b : d;
+        a = a < c ? a : c;
+        b = hi < next ? hi : next;
+    }
+}
+
+// A wave (a block of one) per table, blockIdx.x = DC 0, AC 0, DC 1, AC 1: libjpeg's jpeg_gen_optimal_table.
+// Slot j of a lane is symbol 64 j + lane; slot 4 is symbol 256 in lane 0, the reserved one with count 1, so that no
+// real symbol gets the all-ones code. The merge loop: c1 the non-zero count that is least, the largest symbol on a
+// tie, c2 the same among the rest (one wave reduction that keeps the two least of count << 9 | 511 - symbol); c2's count goes to c1 and
+// every symbol of either tree gets a bit longer and c1's tree id, which is libjpeg's walk of the others[] chains.
+// Then the counts per length, libjpeg's limiting loop to 16 bits and the reserved code's removal (lane 0; libjpeg
+// gives up on a length past 32, the loop itself holds for any, and kMaxLen = 256 is what 257 symbols can reach),
+// huffval by length then value (ballots), and the canonical codes of Annex C in the layout of HuffCodes.
+constexpr int kMaxLen = 256;
+__global__ __launch_bounds__(64) void pt_jpeg_build_tables(EncArgs a)
+{
+    __shared__ int s_raw[kMaxLen + 1], s_bits[kMaxLen + 1];   // symbols per length: as merged, and limited
+    __shared__ int s_cum[18];                                  // [l] the symbols shorter than l (1..17)
+    __shared__ uint32_t s_first[17];                           // [l] the first code of length l
+    __shared__ uint32_t s_code[256];
+    __shared__ uint8_t s_vals[256];
+    const int lane = threadIdx.x, t = blockIdx.x;
+    constexpr unsigned long long kNone = ~0ull;
+    unsigned long long freq[5];
+    int tree[5], size[5];
+#pragma unroll
+    for (int j = 0; j < 5; j++) {
+        freq[j] = j < 4 ? a.hist[t * 256 + 64 * j + lane] : lane == 0 ? 1ull : 0ull;
+        tree[j] = 64 * j + lane;
+        size[j] = 0;
+    }
+    for (;;) {
+        unsigned long long k1 = kNone, k2 = kNone;   // the lane's two least keys, then the wave's
+#pragma unroll
+        for (int j = 0; j < 5; j++) {
+            const unsigned long long k = freq[j] ? freq[j] << 9 | (unsigned long long)(511 - (64 * j + lane)) : kNone;
+            k2 = k < k1 ? k1 : k < k2 ? k : k2;
+            k1 = k < k1 ? k : k1;
+        }
+        wave_min2(k1, k2);
+        if (k2 == kNone) break;   // (the same in every lane)
+        const int c1 = 511 - (int)(k1 & 511), c2 = 511 - (int)(k2 & 511);
+#pragma unroll
+        for (int j = 0; j < 5; j++) {
+            if (64 * j + lane == c1) freq[j] += k2 >> 9;
+            if (64 * j + lane == c2) freq[j] = 0;
+            if (tree[j] == c1 || tree[j] == c2) {
+                size[j]++;
+                tree[j] = c1;
+            }
+        }
+    }
+    for (int i = lane; i <= kMaxLen; i += 64) s_raw[i] = 0;
+    for (int i = lane; i < 256; i += 64) {
+        s_code[i] = 0;
+        s_vals[i] = 0;
+    }
+    __syncthreads();
+    int longest = 0;
+#pragma unroll
+    for (int j = 0; j < 5; j++) {
+        if (size[j]) atomicAdd(&s_raw[size[j]], 1);   // (size <= 256: a merge lengthens a tree of at most 257 symbols)
+        longest = max(longest, size[j]);
+    }
+    for (int o = 32; o > 0; o >>= 1) longest = max(longest, __shfl_xor(longest, o));
+    __syncthreads();
+    for (int i = lane; i <= kMaxLen; i += 64) s_bits[i] = s_raw[i];
+    __syncthreads();
+    if (lane == 0) {
+        for (int i = longest; i > 16; i--)
+            while (s_bits[i] > 0) {
+                int j = i - 2;
+                while (j > 0 && s_bits[j] == 0) j--;   // (the codes are complete, so a shorter length has a symbol)
+                s_bits[i] -= 2;
+                s_bits[i - 1]++;
+                s_bits[j + 1] += 2;
+                s_bits[j]--;
+            }
+        int i = 16;
+        while (i > 0 && s_bits[i] == 0) i--;   // (symbol 256 and one real symbol at least: some length 1..16 has codes)
+        s_bits[i]--;
+        uint32_t code = 0;
+        int cum = 0;
+        for (int l = 1; l <= 16; l++) {
+            s_first[l] = code;
+            s_cum[l] = cum;
+            code = (code + (uint32_t)s_bits[l]) << 1;
+            cum += s_bits[l];
+        }
+        s_cum[17] = cum;
+    }
+    // huffval: the symbols 0..255 by raw length, then by value (slot-major, then lane)
+    int at = 0;
+    for (int l = 1; l <= longest; l++) {
+        if (!s_raw[l]) continue;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const unsigned long long mask = __ballot(size[j] == l);
+            if (size[j] == l) s_vals[at + __popcll(mask & ((1ull << lane) - 1ull))] = (uint8_t)(64 * j + lane);
+            at += __popcll(mask);
+        }
+    }
+    __syncthreads();
+    const int syms = s_cum[17];   // == at: the limiting loop moves codes between lengths and keeps their number
+    const bool dc = !(t & 1);
+    for (int p = lane; p < syms; p += 64) {
+        int l = 1;
+        while (p >= s_cum[l + 1]) l++;
+        const int sym = s_vals[p];
+        if (!dc || sym < 12) s_code[sym] = (s_first[l] + (uint32_t)(p - s_cum[l])) | (uint32_t)l << 16;
+    }
+    __syncthreads();
+    uint32_t* out = dc ? a.codes->dc[t >> 1] : a.codes->ac[t >> 1];
+    for (int i = lane; i < (dc ? 12 : 256); i += 64) out[i] = s_code[i];
+    for (int i = lane; i < 256; i += 64) a.tables->vals[t][i] = s_vals[i];
+    if (lane < 16) a.tables->bits[t][lane] = (uint8_t)s_bits[lane + 1];
+}
+
+// A wave per MCU: every block's AC bit count under the built tables, where pt_jpeg_dct left the Annex K one
+template <int NY> __global__ __launch_bounds__(64 * kWaves) void pt_jpeg_block_bits(EncArgs a)
+{
+    const int lane = threadIdx.x & 63;
+    const size_t m = (size_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
+    if (m >= (size_t)a.mcus_x * a.rows) return;
+    const unsigned row = (unsigned)(m / a.mcus_x), mx = (unsigned)(m % a.mcus_x);
+    for (int c = 0; c < NY + 2; c++) {
+        size_t blk;
+        int v, prev;
+        load_block<NY>(a, row, mx, c, lane, blk, v, prev);
+        const LaneBits b = lane_code_opt(a.codes, lane, v, prev, __ballot(v != 0), c < NY ? 0 : 1);
+        const int ac_bits = wave_sum(lane ? b.zrl_len + b.code_len : 0);
+        if (lane == 0) a.bitoff[blk] = (uint32_t)ac_bits;
+    }
+}
+
+// OPT: the tables pt_jpeg_build_tables derived (a.codes) in place of the Annex K ones
+template <int NY, bool OPT> __global__ __launch_bounds__(256) void pt_jpeg_scan_blocks(EncArgs a)
 {
     __shared__ unsigned sh[4];
     const unsigned row = blockIdx.x;
@@ -235,7 +430,8 @@ template <int NY> __global__ __launch_bounds__(256) void pt_jpeg_scan_blocks(Enc
             const unsigned j = b % (NY + 2), back = dc_back<NY>(j);
             const int dc = a.coef[(base + b) * 64], prev = b >= back ? a.coef[(base + b - back) * 64] : 0;
             const int d = dc - prev, n = 32 - __clz(d < 0 ? -d : d);
-            len = a.bitoff[base + b] + (kCodes.dc[j < NY ? 0 : 1][n] >> 16) + n;
+            if constexpr (OPT) len = a.bitoff[base + b] + (a.codes->dc[j < NY ? 0 : 1][n] >> 16) + n;
+            else len = a.bitoff[base + b] + (kCodes.dc[j < NY ? 0 : 1][n] >> 16) + n;
         }
         unsigned total;
         const unsigned at = carry + block_scan(len, sh, total);
@@ -248,7 +444,8 @@ template <int NY> __global__ __launch_bounds__(256) void pt_jpeg_scan_blocks(Enc
     for (unsigned i = threadIdx.x; i < (carry + 127) / 128; i += 256) z[i] = make_uint4(0, 0, 0, 0);
 }
 
-template <int NY> __global__ __launch_bounds__(64 * kWaves) void pt_jpeg_emit(EncArgs a)
+// OPT: the built tables, under which a lane's share may be 74 bits: the ZRLs apart from the code, in a four-word window
+template <int NY, bool OPT> __global__ __launch_bounds__(64 * kWaves) void pt_jpeg_emit(EncArgs a)
 {
     const int lane = threadIdx.x & 63;
     const size_t m = (size_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
@@ -260,6 +457,20 @@ template <int NY> __global__ __launch_bounds__(64 * kWaves) void pt_jpeg_emit(En
         const int v = a.coef[blk * 64 + lane];
         const unsigned at_row = mx * (NY + 2) + c, back = dc_back<NY>((unsigned)c);
         const int prev = at_row >= back ? a.coef[(blk - back) * 64] : 0;   // the prediction restarts with every row
+        if constexpr (OPT) {
+            const LaneBits b = lane_code_opt(a.codes, lane, v, prev, __ballot(v != 0), c < NY ? 0 : 1);
+            const int len = b.zrl_len + b.code_len;
+            const unsigned at = a.bitoff[blk] + (unsigned)(wave_scan(len, lane) - len);
+            if (len) {
+                uint32_t w[4];
+                lane_window(b, at, w);
+                uint32_t* dst = words + (at >> 5);   // (a word past the row's bits is zero here and is not touched)
+#pragma unroll
+                for (int i = 0; i < 4; i++)
+                    if (w[i]) atomicOr(dst + i, w[i]);
+            }
+            continue;
+        }
         unsigned long long bits;
         int len;
         lane_code(lane, v, prev, __ballot(v != 0), c < NY ? 0 : 1, bits, len);
@@ -361,8 +572,17 @@ template <int HS, int VS> static void launch_blocks(const ptj::EncArgs* a, hipSt
     const size_t n_mcu = (size_t)a->mcus_x * a->rows;
     const dim3 mcus((unsigned)((n_mcu + ptj::kWaves - 1) / ptj::kWaves));
     hipLaunchKernelGGL((ptj::pt_jpeg_dct<HS, VS>), mcus, dim3(64 * ptj::kWaves), 0, s, *a);
-    hipLaunchKernelGGL((ptj::pt_jpeg_scan_blocks<HS * VS>), dim3(a->rows), dim3(256), 0, s, *a);
-    hipLaunchKernelGGL((ptj::pt_jpeg_emit<HS * VS>), mcus, dim3(64 * ptj::kWaves), 0, s, *a);
+    if (a->codes) {   // optimised tables: count the symbols (a->hist is zero), build the tables, measure with them
+        const dim3 some(mcus.x < ptj::kHistBlocks ? mcus.x : ptj::kHistBlocks);
+        hipLaunchKernelGGL((ptj::pt_jpeg_hist<HS * VS>), some, dim3(64 * ptj::kWaves), 0, s, *a);
+        hipLaunchKernelGGL(ptj::pt_jpeg_build_tables, dim3(4), dim3(64), 0, s, *a);
+        hipLaunchKernelGGL((ptj::pt_jpeg_block_bits<HS * VS>), mcus, dim3(64 * ptj::kWaves), 0, s, *a);
+        hipLaunchKernelGGL((ptj::pt_jpeg_scan_blocks<HS * VS, true>), dim3(a->rows), dim3(256), 0, s, *a);
+        hipLaunchKernelGGL((ptj::pt_jpeg_emit<HS * VS, true>), mcus, dim3(64 * ptj::kWaves), 0, s, *a);
+        return;
+    }
+    hipLaunchKernelGGL((ptj::pt_jpeg_scan_blocks<HS * VS, false>), dim3(a->rows), dim3(256), 0, s, *a);
+    hipLaunchKernelGGL((ptj::pt_jpeg_emit<HS * VS, false>), mcus, dim3(64 * ptj::kWaves), 0, s, *a);
 }
 
 // colour conversion .. the stream's length: what runs before the host can size the stream buffer

@@ -171,18 +171,24 @@ inline size_t spill_slab(int p, size_t lanes) { return (size_t)p * lanes * kSpil
 // ZRL is 11 bits, an EOB 4), so the longest block has 63 non-zero ACs of a 16-bit code and 10 value bits each and a
 // DC of an 11-bit code and 11 value bits, 1660 bits = 207.5 B; the quantiser clamps to those categories. The
 // stream: every byte of a row may be 0xFF and take a stuffed 0x00, and every row ends in a 2-byte RSTm or EOI.
+// With Huffman tables built for the frame (pt_canvas_encode_jpeg_opt, optimize = 1) any code may be 16 bits long,
+// the DC's too, and a ZRL or EOB still costs no more than the coefficients it stands for (16 bits against 26 each):
+// 63 x (16 + 10) + 16 + 11 = 1665 bits = 208.125 B, past 208. kJpegOptBlockBytes is the next multiple of 16 (a
+// row's zeroing runs in uint4): 224 B = 1792 bits. A row then stays below 2^24 bytes as pt_jpeg_scan_rows needs:
+// 8192 x 3 x 2 x 224 + 2 = 11 010 050.
 constexpr size_t kJpegBlockBytes = 208;
+constexpr size_t kJpegOptBlockBytes = 224;
 constexpr size_t kJpegTile = 1024;      // bytes of a row one block of the stuffing kernels takes (256 lanes x 4 B)
-constexpr size_t kJpegHeader = 629;    // SOI .. SOS: what the host writes before the stream
+constexpr size_t kJpegHeader = 629;    // SOI .. SOS: what the host writes before the stream (Annex K tables)
 struct JpegLayout {
     size_t mcus_x, blocks_row, rows, row_stride, tiles;
     size_t coef, bitoff, bits, tileoff, rowbits, rowlen, rowoff, total, bytes;
-    JpegLayout(int width, int height, int hs = 1, int vs = 1)
+    JpegLayout(int width, int height, int hs = 1, int vs = 1, size_t block_bytes = kJpegBlockBytes)
     {
         mcus_x = ((size_t)width + 8 * hs - 1) / (8 * hs);
         blocks_row = mcus_x * (hs * vs + 2);
         rows = ((size_t)height + 8 * vs - 1) / (8 * vs);
-        row_stride = blocks_row * kJpegBlockBytes;
+        row_stride = blocks_row * block_bytes;
         tiles = (row_stride + kJpegTile - 1) / kJpegTile;
         const size_t blocks = blocks_row * rows;
         Carve c;
@@ -203,6 +209,23 @@ inline size_t jpeg_out_room(size_t need, size_t stream_max)
     const size_t want = need + need / 4 < 65536 ? 65536 : need + need / 4;
     return want < stream_max ? want : stream_max;
 }
+// What the optimised tables add to that workspace, in a slab of its own so that the standard call's does not change,
+// the same for every canvas: hist [4 x 256 x 8 B] the symbol counts (DC 0, AC 0, DC 1, AC 1; 64-bit: a symbol of a
+// 65535 x 65535 canvas may occur more than 2^32 times) | codes [ptj::HuffCodes, 2144 B] | total [8 B] the stream's
+// length, which takes the place of JpegLayout::total, and right behind it tables [ptj::OptTables, 1088 B], so that
+// one copy fetches both.
+struct JpegOptLayout {
+    static constexpr size_t kHist = 4 * 256 * 8, kCodes = (2 * 12 + 2 * 256) * 4, kTables = 4 * 16 + 4 * 256;
+    size_t hist, codes, total, tables, bytes;
+    JpegOptLayout()
+    {
+        Carve c;
+        hist = c.take(kHist); codes = c.take(kCodes);
+        total = c.take(8 + kTables);
+        tables = total + 8;
+        bytes = c.at;
+    }
+};
 
 // Frame overlap of the megakernel's draws (pt_capi.cpp, Dev): the sequencing state. Draw k = mk_seq takes buffer
 // set k % (depth + lag) and side stream k % depth, and its path tracing waits for the mark of draw

@@ -23,7 +23,7 @@
 //   engine.denoise(beautyRT, normalRT, albedoRT, dstRT, opts) -> pt_denoise (extension: a-trous filter over them)
 //   effect.setMomentTarget(momentsRT)             -> pt_set_moment_target (extension: accumulated luminance moments)
 //   engine.denoiseVariance(beautyRT, normalRT, albedoRT, momentsRT, dstRT, opts) -> pt_denoise_variance
-//   engine.encodeCanvasJPEG(quality, subsampling) -> pt_canvas_encode_jpeg_sub (extension: the canvas as a JPEG file)
+//   engine.encodeCanvasJPEG(quality, subsampling, optimize) -> pt_canvas_encode_jpeg_opt (extension: the canvas as a JPEG file)
 'use strict';
 const fs = require('fs');
 const path = require('path');
@@ -190,16 +190,18 @@ function install(BABYLON, opts) {
       check(this._pt, addon.pt_read_pixels(this._pt, null, out), 'readPixels');
       return out;
     }
-    // MI355X extension (pt_canvas_encode_jpeg_sub): the canvas as a baseline JPEG file (a restart interval per MCU
+    // MI355X extension (pt_canvas_encode_jpeg_opt): the canvas as a baseline JPEG file (a restart interval per MCU
     // row) encoded on the device, as a Buffer; the bytes are libjpeg-turbo's for the same pixels, quality and
-    // subsampling (0 4:4:4, 1 4:2:2, 2 4:2:0). The buffer starts at the last call's length; the call is repeated
-    // once when it answers that it is too small.
-    encodeCanvasJPEG(quality = 90, subsampling = 0) {
+    // subsampling (0 4:4:4, 1 4:2:2, 2 4:2:0), with `optimize` those of its optimize_coding: Huffman tables built
+    // on the device for this canvas, a shorter file of the same pixels. The buffer starts at the last call's
+    // length; the call is repeated once when it answers that it is too small.
+    encodeCanvasJPEG(quality = 90, subsampling = 0, optimize = false) {
+      const opt = optimize ? 1 : 0;
       let buf = Buffer.allocUnsafe(this._jpegCapacity || 65536);
-      let [rc, size] = addon.pt_canvas_encode_jpeg_sub(this._pt, quality | 0, subsampling | 0, buf);
+      let [rc, size] = addon.pt_canvas_encode_jpeg_opt(this._pt, quality | 0, subsampling | 0, opt, buf);
       if (rc !== 0 && size > buf.length) {
         buf = Buffer.allocUnsafe(size);
-        [rc, size] = addon.pt_canvas_encode_jpeg_sub(this._pt, quality | 0, subsampling | 0, buf);
+        [rc, size] = addon.pt_canvas_encode_jpeg_opt(this._pt, quality | 0, subsampling | 0, opt, buf);
       }
       check(this._pt, rc, 'encodeCanvasJPEG');
       this._jpegCapacity = Math.max(buf.length, size);

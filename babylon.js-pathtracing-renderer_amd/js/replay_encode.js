@@ -1,11 +1,12 @@
 // replay_encode.js — replays a recorded per-frame draw stream (tests/golden/*.json) through the
 // Babylon-shaped shim and the N-API addon, then encodes the canvas on the device
-// (Engine.encodeCanvasJPEG -> pt_canvas_encode_jpeg) and writes the file. The JavaScript host's view of the
+// (Engine.encodeCanvasJPEG -> pt_canvas_encode_jpeg_opt) and writes the file. The JavaScript host's view of the
 // encoder: what a Node host serving frames to a browser does after engine.stepFrame(). Tests compare it byte
 // for byte with the Python binding's and with the reference encoder over the canvas written beside it.
 //
-// usage: node replay_encode.js <stream.json> <payload_dir> <out_prefix> [frames] [quality] [subsampling]
-//   subsampling 0 (4:4:4, the default), 1 (4:2:2) or 2 (4:2:0)
+// usage: node replay_encode.js <stream.json> <payload_dir> <out_prefix> [frames] [quality] [subsampling] [optimize]
+//   subsampling 0 (4:4:4, the default), 1 (4:2:2) or 2 (4:2:0); optimize 0 (the Annex K Huffman tables, the default)
+//   or 1 (tables built for the frame)
 //   payload_dir as for replay_stream.js: bluenoise.u8 and, for glTF streams, bvh.f32 / tri.f32, hdr.f32
 //   writes <out_prefix>.jpg and <out_prefix>.canvas.u8 (RGBA8, rows bottom-up)
 'use strict';
@@ -13,11 +14,12 @@ const fs = require('fs');
 const path = require('path');
 const { install } = require('./babylon_pt.js');
 
-const [streamPath, payloadDir, outPrefix, framesArg, qualityArg, subsamplingArg] = process.argv.slice(2);
+const [streamPath, payloadDir, outPrefix, framesArg, qualityArg, subsamplingArg, optimizeArg] = process.argv.slice(2);
 const meta = JSON.parse(fs.readFileSync(streamPath, 'utf8'));
 const nFrames = framesArg ? parseInt(framesArg, 10) : meta.frames.length;
 const quality = qualityArg ? parseInt(qualityArg, 10) : 90;
 const subsampling = subsamplingArg ? parseInt(subsamplingArg, 10) : 0;
+const optimize = optimizeArg ? parseInt(optimizeArg, 10) !== 0 : false;
 const BABYLON = {};
 const errors = [];
 const size = { width: meta.width, height: meta.height };
@@ -57,7 +59,7 @@ for (let i = 0; i < nFrames; i++) {
     renderer.render(w, call.target ? tex[call.target] : null);
   }
 }
-fs.writeFileSync(outPrefix + '.jpg', engine.encodeCanvasJPEG(quality, subsampling));
+fs.writeFileSync(outPrefix + '.jpg', engine.encodeCanvasJPEG(quality, subsampling, optimize));
 fs.writeFileSync(outPrefix + '.canvas.u8', Buffer.from(engine.readCanvas().buffer));
 if (errors.length) { console.error(errors.join('\n')); process.exit(2); }
 engine.dispose();

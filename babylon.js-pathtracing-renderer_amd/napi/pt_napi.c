@@ -300,6 +300,19 @@ static napi_value CanvasEncodeJpegSub(napi_env env, napi_callback_info info)
     CHECK(napi_set_element(env, r, 1, num(env, (double)size)));
     return r;
 }
+/* pt_canvas_encode_jpeg_opt(ctx, quality, subsampling, optimize, out: Uint8Array) -> [status, size], as above */
+static napi_value CanvasEncodeJpegOpt(napi_env env, napi_callback_info info)
+{
+    napi_value a[MAXARGS], r; if (args(env, info, a, 5) < 0) return NULL;
+    size_t cap, size = 0; uint8_t* p = (uint8_t*)bytes_of(env, a[4], &cap);
+    if (!p) { napi_throw_type_error(env, NULL, "typed array expected"); return NULL; }
+    const int rc = pt_canvas_encode_jpeg_opt((pt_ctx*)handle(env, a[0]), i32(env, a[1]), i32(env, a[2]), i32(env, a[3]),
+                                             p, cap, &size);
+    CHECK(napi_create_array_with_length(env, 2, &r));
+    CHECK(napi_set_element(env, r, 0, num(env, rc)));
+    CHECK(napi_set_element(env, r, 1, num(env, (double)size)));
+    return r;
+}
 static napi_value WritePixels(napi_env env, napi_callback_info info)
 {
     napi_value a[MAXARGS]; if (args(env, info, a, 3) < 0) return NULL;
@@ -502,6 +515,7 @@ static napi_value Init(napi_env env, napi_value exports)
         { "pt_render_target_resize", RtResize }, { "pt_texture_size", TexSize }, { "pt_texture_destroy", TexDestroy },
         { "pt_render", Render }, { "pt_read_pixels", ReadPixels }, { "pt_write_pixels", WritePixels },
         { "pt_canvas_encode_jpeg", CanvasEncodeJpeg }, { "pt_canvas_encode_jpeg_sub", CanvasEncodeJpegSub },
+        { "pt_canvas_encode_jpeg_opt", CanvasEncodeJpegOpt },
         { "pt_set_row_partition", RowPartition }, { "pt_set_backend", SetBackend }, { "pt_set_output_partition", SetOutputPartition }, { "pt_canvas_wrap", CanvasWrap }, { "pt_set_bvh_layout", SetBvhLayout },
         { "pt_bvh_layout_used", BvhLayoutUsed }, { "pt_set_stream", SetStream }, { "pt_texture_device_ptr", TexDevicePtr },
         { "pt_last_render_ms", LastRenderMs }, { "pt_timing_begin", TimingBegin }, { "pt_timing_end", TimingEnd },

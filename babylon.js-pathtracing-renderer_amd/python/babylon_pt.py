@@ -38,7 +38,8 @@ SYMBOLS = [
     "pt_set_float", "pt_set_int", "pt_set_texture",
     "pt_texture_create_rgba32f", "pt_texture_create_rgba8", "pt_render_target_create", "pt_render_target_wrap",
     "pt_render_target_resize", "pt_texture_size", "pt_texture_destroy",
-    "pt_render", "pt_read_pixels", "pt_canvas_encode_jpeg", "pt_canvas_encode_jpeg_sub", "pt_write_pixels",
+    "pt_render", "pt_read_pixels", "pt_canvas_encode_jpeg", "pt_canvas_encode_jpeg_sub", "pt_canvas_encode_jpeg_opt",
+    "pt_write_pixels",
     "pt_set_row_partition", "pt_set_output_partition", "pt_canvas_wrap", "pt_set_backend", "pt_set_bvh_layout", "pt_bvh_layout_used", "pt_set_stream", "pt_texture_device_ptr", "pt_last_render_ms", "pt_timing_begin", "pt_timing_end", "pt_timing_latency",
     "pt_set_counting", "pt_read_counters", "pt_reset_counters", "pt_queue_stats", "pt_cont_stats", "pt_set_feature_targets", "pt_denoise", "pt_set_moment_target", "pt_denoise_variance", "pt_math_probe", "pt_math_exhaustive", "pt_bvh_build", "pt_bvh_build_gpu", "pt_jpeg_size", "pt_jpeg_decode_rgba8", "pt_version",
 ]
@@ -76,6 +77,7 @@ def lib():
         "pt_write_pixels": ([vp, vp, vp, ctypes.c_size_t], i32),
         "pt_canvas_encode_jpeg": ([vp, i32, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)], i32),
         "pt_canvas_encode_jpeg_sub": ([vp, i32, i32, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)], i32),
+        "pt_canvas_encode_jpeg_opt": ([vp, i32, i32, i32, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)], i32),
         "pt_set_row_partition": ([vp, i32, i32], i32), "pt_texture_device_ptr": ([vp], vp),
         "pt_set_backend": ([vp, i32], i32), "pt_set_output_partition": ([vp, i32], i32),
         "pt_canvas_wrap": ([vp, i32, i32, vp], i32), "pt_set_stream": ([vp, vp], i32),
@@ -153,21 +155,23 @@ class Engine:
         self.check(lib().pt_read_pixels(self.ctx, None, out.ctypes.data, out.nbytes), "pt_read_pixels")
         return out
 
-    def encode_canvas_jpeg(self, quality=90, subsampling=0):
-        """MI355X extension (pt_canvas_encode_jpeg_sub): the canvas as a baseline JPEG file (a restart interval
+    def encode_canvas_jpeg(self, quality=90, subsampling=0, optimize=False):
+        """MI355X extension (pt_canvas_encode_jpeg_opt): the canvas as a baseline JPEG file (a restart interval
         per MCU row), encoded on the device; the bytes are libjpeg-turbo's for the same pixels, quality and
-        subsampling (Pillow's numbering: 0 4:4:4, 1 4:2:2, 2 4:2:0). The buffer starts at the last call's length
-        and the call is repeated once when the answer is that it is too small (PT_ERR_ARG with the needed length
-        in size)."""
+        subsampling (Pillow's numbering: 0 4:4:4, 1 4:2:2, 2 4:2:0), and with `optimize` for Pillow's
+        optimize=True: Huffman tables built on the device for this canvas, a shorter file of the same pixels. The
+        buffer starts at the last call's length and the call is repeated once when the answer is that it is too
+        small (PT_ERR_ARG with the needed length in size)."""
         cap = getattr(self, "_jpeg_capacity", 1 << 16)
         for _ in range(2):
             buf = (ctypes.c_uint8 * cap)()
             size = ctypes.c_size_t(0)
-            rc = lib().pt_canvas_encode_jpeg_sub(self.ctx, int(quality), int(subsampling), buf, cap, ctypes.byref(size))
+            rc = lib().pt_canvas_encode_jpeg_opt(self.ctx, int(quality), int(subsampling), int(optimize), buf, cap,
+                                                 ctypes.byref(size))
             if rc == 0 or size.value <= cap:
                 break
             cap = size.value
-        self.check(rc, "pt_canvas_encode_jpeg_sub")
+        self.check(rc, "pt_canvas_encode_jpeg_opt")
         self._jpeg_capacity = max(cap, size.value)
         return bytes(memoryview(buf)[:size.value])
 

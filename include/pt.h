@@ -179,6 +179,26 @@ int pt_canvas_encode_jpeg(pt_ctx* ctx, int quality, uint8_t* dst, size_t capacit
 enum pt_jpeg_subsampling { PT_JPEG_444 = 0, PT_JPEG_422 = 1, PT_JPEG_420 = 2 };   /* Pillow's numbering */
 int pt_canvas_encode_jpeg_sub(pt_ctx* ctx, int quality, int subsampling,
                               uint8_t* dst, size_t capacity, size_t* size);
+/* The same with the choice of Huffman tables; pt_canvas_encode_jpeg_sub(ctx, q, s, ...) is
+ * pt_canvas_encode_jpeg_opt(ctx, q, s, 0, ...), and everything said there holds: it observes like pt_read_pixels and
+ * synchronises, encodes part 0's gathered canvas on a context of several parts, writes no texture, counter,
+ * statistic or timing window, and returns PT_ERR_ARG with *size set and dst untouched when capacity is too small.
+ * optimize 0: the Annex K tables; the bytes, kernels and workspace of pt_canvas_encode_jpeg_sub.
+ * optimize 1: Huffman tables built on the device for this canvas. The bytes are those libjpeg-turbo writes for the
+ * same pixels, quality and subsampling with optimize_coding and a restart marker per MCU row
+ * (tests/jpeg_enc_opt_ref.py); a decoder reconstructs the same pixels as from the optimize 0 file, which was 2 to
+ * 30 % longer on rendered frames. What it changes:
+ *   statistics  four histograms, DC 0, AC 0, DC 1, AC 1 (Y tables 0, Cb and Cr tables 1), of exactly the symbols
+ *               coded: every block's DC category, per non-zero AC run >> 4 ZRLs and (run & 15) << 4 | size, an EOB
+ *               when the last coefficient is zero; dummy Y blocks count.
+ *   tables      libjpeg's jpeg_gen_optimal_table per histogram: a reserved symbol of count 1, Huffman's merges with
+ *               the least count first and the largest symbol on a tie, code lengths limited to 16 in libjpeg's order,
+ *               the reserved all-ones code removed, the symbols listed by length and then value.
+ *   header      the same segments in the same order; each DHT carries its table's bits[16] and symbols, so the
+ *               header's length (629 with the Annex K tables) varies with the pixels.
+ * PT_ERR_ARG also for an optimize other than 0 or 1. */
+int pt_canvas_encode_jpeg_opt(pt_ctx* ctx, int quality, int subsampling, int optimize,
+                              uint8_t* dst, size_t capacity, size_t* size);
 /* Upload rows of a render target (RGBA32F), used to seed the history buffer in tests and to
  * land gathered bands on the root in multi-GPU runs. */
 int pt_write_pixels(pt_ctx* ctx, pt_texture* tex, const void* src, size_t bytes);
