@@ -368,6 +368,46 @@ PT_D void meshHit(const TraceArgs& a, float triID, float triU, float triV, Hit& 
     h.id = meshObjectId<PROG>(a);
 }
 
+// Dead shadow segments: a path that has just sampled the light (`s.sampleLight` set by this step) with a
+// throughput of bitwise +0.0f in all three components ends here, its shadow segment not traced. The
+// weight of the sample is a product of max(0, cosine) terms (sampleQuadLight: the surface faces away from
+// the sampled light point, or lies in or above the light's plane - the whole ceiling), so exact zeros are
+// common. shadeStep then returns false with `accum` untouched, which is what the skipped segment leaves:
+//  * `accum` is +0 on entry: it is initialised to +0 with the path (radiance(), pt_persist's refill), or
+//    per step (pt_cont, wf_shade), and only a step that ends the path assigns it (js/GLTFModelPathTracing_
+//    FragmentShader.js:351-609, oracle/ptoracle.c's calculate_radiance: every assignment is followed by break).
+//  * In the skipped segment `bounces >= 1`, `diffuseCount >= 1`, `specular` is false and the previous
+//    hitType is DIFFUSE or CLEARCOAT_DIFFUSE (the diffuse tail just ran). A miss returns false at once in
+//    these programs (no environment). A hit writes the G-buffer only at bounce 0 or at bounce 1 after
+//    METAL: neither holds. A LIGHT hit sets the sharpness only with diffuseCount == 0 (it is not), assigns
+//    accum = mask * hitColor and ends; any other hit ends at `if (sampleLight) return false` before
+//    any other statement. So no G setter fires, and accum is +0 or mask * hitColor.
+//  * Every hitColor that can reach that product is a finite, non-negative constant of the host
+//    (pt_capi.cpp setup_scene: the walls, the spheres, the light's emission 10; objectMaterial: the quadric
+//    shapes' table, the mesh's 1); the PBR decode that reads a colour from a texture comes after the
+//    sampleLight return. +0 * c is +0 for every finite c >= 0, and max3s(+0, 0) is +0. A mask component
+//    that is -0 (a negative throughput times +0) or NaN (an infinite one) does not compare equal in the
+//    bits: such a path takes the old way.
+//  * The path's rng / blue-noise state, ray and counters are read by nothing after the path: they die
+//    with it. So radianceOut gets the same radiance bits (+0, +0, +0) and the same sharpness, hence the
+//    same alpha flag, as after the traced segment.
+// Off in the sky programs (the skipped miss would assign mask * skyColor, whose finiteness depends on the
+// sun-direction uniform: data) and the HDRI program (mask * texel: data). Off in the counting variants: they
+// price the reference's work, every segment of it.
+template <int PROG, bool COUNT> constexpr bool kDeadShadow = !COUNT && !kIsSky<PROG> && !kIsHdri<PROG>;
+template <int PROG, bool COUNT>
+PT_D bool deadShadow(const TraceArgs& a, const PState& s)
+{
+    const bool zero = (__float_as_uint(s.mask.x) | __float_as_uint(s.mask.y) | __float_as_uint(s.mask.z)) == 0u;
+#ifdef PT_DEADSEG_STAT   // experiment builds: the timed kernels' light-sampling segments and those of zero throughput,
+    if (!COUNT) {        // in every program, also where the rule is off (tools/deadseg_share.py)
+        atomicAdd(&a.counters[C_SEGMENTS], 1ull);
+        if (zero) atomicAdd(&a.counters[C_HIT], 1ull);
+    }
+#endif
+    return kDeadShadow<PROG, COUNT> && zero;
+}
+
 // The loop body after SceneIntersect, for the intersection `h` of the current ray. Returns false
 // when the path has ended; `accum` then holds the radiance before the final max(accum, 0).
 template <int PROG, bool COUNT, class G>
@@ -491,6 +531,7 @@ PT_D bool shadeStep(const TraceArgs& a, Path& p, PState& s, G& g, f3& accum, Hit
         diffuseTail = true;
     }
     if (diffuseTail) {
+        bool dead = false;
         s.diffuseCount++;
         s.mask = s.mask * h.color;
         s.specular = false;
@@ -499,20 +540,20 @@ PT_D bool shadeStep(const TraceArgs& a, Path& p, PState& s, G& g, f3& accum, Hit
         } else if (hdri) {   // shadow ray into the sun's lobe (js/HDRIEnvironmentPathTracing_FragmentShader.js:395-400)
             p.rd = specularLobeDir(p, a.sky.sun, 0.03f);
             s.mask = s.mask * (gmax(0.0f, dot(p.rd, nl)) * a.sun_weight);
-            if (hitType == DIFFUSE || bounces < 3) s.sampleLight = true;
+            if (hitType == DIFFUSE || bounces < 3) { s.sampleLight = true; dead = deadShadow<PROG, COUNT>(a, s); }
         } else if (sky) {   // shadow ray into the sun's lobe (js/PhysicalSkyModel_FragmentShader.js:237-243)
             p.rd = specularLobeDir(p, a.sky.sun, 0.1f);
             s.mask = s.mask * (gmax(0.0f, dot(p.rd, nl)) * 0.05f);
-            if (hitType == DIFFUSE || bounces < 3) s.sampleLight = true;
+            if (hitType == DIFFUSE || bounces < 3) { s.sampleLight = true; dead = deadShadow<PROG, COUNT>(a, s); }
         } else {
             float w;
             f3 dl = sampleQuadLight(p, a, x, nl, w);
             s.mask = s.mask * w;
             p.rd = dl;
-            if (hitType == DIFFUSE || bounces < 3) s.sampleLight = true;
+            if (hitType == DIFFUSE || bounces < 3) { s.sampleLight = true; dead = deadShadow<PROG, COUNT>(a, s); }
         }
         p.ro = x + nl * a.eps;
-        return more;
+        return more && !dead;
     }
     if (hitType == METAL) {
         s.mask = s.mask * h.color;

@@ -178,6 +178,8 @@ PT_D bool bounceStep(const TraceArgs& a, Path& p, PState& s, G& g, f3& accum, fl
     //    the hit's normal, and a PBR hit reads its maps. Not in the textured variants (their PBR meshes
     //    never qualify, and the test alone costs the helmet 1 %).
     // (profiles/r04k_envmx_anyhit.txt, r04q_envmx_anyhit_last.txt)
+    // A shadow ray whose path carries a throughput of exactly +0 is not traced at all in the room programs:
+    // shadeStep ends the path where it samples the light (pt_program.h deadShadow).
     const bool lastOk = !kHasTex<PROG> && !a.uses_albedo &&
                         (a.model_mat == DIFFUSE || a.model_mat == METAL || a.model_mat == TRANSPARENT);
     const bool firstHit = s.sampleLight || (s.bounce == 5 && lastOk);
