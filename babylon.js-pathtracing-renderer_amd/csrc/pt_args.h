@@ -239,6 +239,15 @@ struct BlendArgs {
     unsigned* cont_bins;    // (PT_CONT_SORT) the record sort's kSortBins totals, zeroed here (NULL: none)
 };
 
+// pt_output_f1: a megakernel draw's pending blend folded into the screenOutput that follows it in the
+// render loop (pt_plan.h MainPlan). The tile stage forms each staged texel as historyBlend(b.prev, b.rad) instead of
+// loading it from o.acc (unused), and a tile's own 16x16 texels are stored to b.out, which must not be b.prev: the
+// neighbouring tiles read b.prev's halo texels. o.copy_dst is NULL: the frame's screenCopy stays pending.
+struct FusedArgs {
+    OutputArgs o;
+    BlendArgs b;
+};
+
 // pt_feature_fold: a draw's G-buffer sample folded into the effect's feature targets in place, over the owned
 // 16-row bands, by the beauty's history rule (include/pt.h pt_set_feature_targets). g0 / g1: the staged sample
 // (normal.xyz, id | colour.xyz, -), `stride` pixels per row: the megakernel's staging slab (the target's

@@ -20,7 +20,10 @@
 //                      schedules (draw_queued) run on the main stream alone;
 //   SCREEN_COPY     -> pt_copy over the owned bands, deferred to fuse with the next screenOutput;
 //   SCREEN_OUTPUT   -> pt_output into the canvas (RGBA8) or an RGBA32F target, with a deferred copy
-//                      and order build riding along.
+//                      and order build riding along; in the render loop (whole frames of up to 8192 tiles) the
+//                      megakernel draw's pt_blend waits for it too, and the three run as one pass, pt_output_f1,
+//                      that leaves the copy target stale (pt_plan.h MainPlan; flush_deferred runs what is
+//                      pending before anything else could observe it).
 // dev_denoise (pt_denoise) is no draw: the à-trous filter's prep and passes (pt_denoise.hip) on the main stream.
 // dev_denoise_variance (pt_denoise_variance) likewise (pt_denoise_var.hip), with a slab of its own.
 // The main stream is the context's own or the caller's (dev_set_stream); per-draw timing events are off
@@ -57,6 +60,7 @@ hipError_t pt_launch_feature_fold(const pt::FoldArgs* a, int bands, hipStream_t 
 hipError_t pt_launch_cont_sort(const pt::SortArgs* a, size_t cap, hipStream_t s);
 hipError_t pt_launch_cont(int prog, const pt::TraceArgs* a, int waves, hipStream_t s);
 hipError_t pt_launch_output(const pt::OutputArgs* a, hipStream_t s, int waves);
+hipError_t pt_launch_output_fused(const pt::FusedArgs* a, hipStream_t s);
 hipError_t pt_launch_denoise(const pt::DenoiseArgs* a, hipStream_t s);
 hipError_t pt_launch_denoise_var(const pt::DenoiseVarArgs* a, hipStream_t s);
 hipError_t pt_launch_jpeg_measure(const ptj::EncArgs* a, hipStream_t s);
@@ -98,6 +102,7 @@ struct DevTex {
     int sampling = PT_SAMPLING_NEAREST;
     int invert_y = 0;
     bool external = false;   // caller-owned device memory (dev_render_target_wrap)
+    bool exposed = false;    // its device pointer was handed out (dev_texture_expose): the caller may read it like its own
     unsigned long long gen = 0;   // bumped by every host write of the texels
     // child-pair BVH records derived from this texture and the triangle texture drawn with it
     // (pt_pairs.h), valid while both keep the generations they were built from
@@ -127,9 +132,13 @@ struct Dev {
     bool counting = false;
     int num_parts = 1, part = 0;
     bool output_partition = false;
-    // screenCopy deferred to ride along with the next screenOutput of the same source (flushed as
-    // its own kernel before anything else could observe the target: flush_copy)
-    struct { bool on; DevTex* src; DevTex* dst; int num_parts, part; } pending_copy = {};
+    // The main stream's deferred passes (pt_plan.h MainPlan; its textures are DevTex*): a screenCopy waits to ride
+    // along with the next screenOutput of the same source, and a megakernel draw's blend (k.fuse_blend) for the
+    // loop's screenCopy and screenOutput, which then run as one pass that leaves the copy target stale. Anything
+    // else that could observe either texture first runs what is pending as its own kernels (flush_deferred).
+    pt::MainPlan plan;
+    struct { pt::BlendArgs b; int bands, waves; } pending_blend = {};   // the waiting blend's launch (plan.blend.on)
+    uint64_t fused_passes = 0, stale_copies = 0;   // pt_fuse_stats: fused passes, pt_copy launches for a stale texture
     bool canvas_external = false;     // dev_canvas_wrap: caller-owned canvas memory
     pt::Knobs k;                      // the tunables, read from the environment once (pt_knobs.h)
     int backend = PT_BACKEND_MEGAKERNEL;
@@ -635,6 +644,55 @@ int flush_order(Dev* c)
     return PT_OK;
 }
 
+int launch_copy(Dev* c, const DevTex* src, DevTex* dst, int num_parts, int part)
+{
+    pt::CopyArgs a{ dst->w, dst->h, num_parts, part, (const float4*)src->d, (float4*)dst->d };
+    const int gx = (dst->w + 255) / 256, gy = pt::bands_owned(dst->h, num_parts, part);
+    if (gy > 0) HIPCHK(c, pt_launch_copy(&a, gx, gy, c->stream));
+    return PT_OK;
+}
+
+// What pt::MainPlan asks for before the draw at hand, as kernels of their own: a deferred screenCopy (timed as a
+// screenCopy draw) and a waiting blend, in place as its draw asked
+int run_deferred(Dev* c, const pt::MainPlan::Op& op)
+{
+    if (op.kind == pt::MainPlan::COPY) {
+        int rc = begin_draw(c, PT_PROG_SCREEN_COPY);
+        if (rc) return rc;
+        c->stale_copies++;
+        if ((rc = launch_copy(c, (const DevTex*)op.src, (DevTex*)op.dst, op.num_parts, op.part))) return rc;
+        return end_draw(c, PT_PROG_SCREEN_COPY);
+    }
+    if (op.kind == pt::MainPlan::BLEND) {
+        pt::BlendArgs& b = c->pending_blend.b;
+        b.prev = (const float4*)((const DevTex*)op.src)->d;
+        b.out = (float4*)((const DevTex*)op.dst)->d;
+        HIPCHK(c, pt_launch_blend(&b, c->pending_blend.bands, c->stream, c->pending_blend.waves));
+    }
+    return PT_OK;
+}
+int run_deferred(Dev* c, const pt::MainPlan::Ops& ops)
+{
+    for (int i = 0; i < ops.n; i++)
+        if (int rc = run_deferred(c, ops.op[i])) return rc;
+    return PT_OK;
+}
+
+// everything deferred, now: before anything that could observe the loop's textures or the buffer set's counters
+int flush_deferred(Dev* c)
+{
+    pt::MainPlan::Ops ops;
+    c->plan.observe(ops);
+    return run_deferred(c, ops);
+}
+// ... the waiting blend alone (it keeps the buffer sets' record totals); a stale texture stays stale
+int flush_blend(Dev* c)
+{
+    pt::MainPlan::Ops ops;
+    c->plan.resolve_blend(ops);
+    return run_deferred(c, ops);
+}
+
 // A path-tracing draw's arguments from the effect's uniforms and samplers, checked; `mesh`: the program walks a BVH
 // (whose child-pair records are built here when its textures changed)
 int trace_args(DevFx* fx, DevTex* target, pt::TraceArgs& a, bool& mesh)
@@ -790,8 +848,10 @@ int draw_queued(DevFx* fx, DevTex* target, pt::TraceArgs& a, bool mesh, int gx, 
     return PT_OK;
 }
 
-// The megakernel draw over gx x gy tiles: plan (pt_plan.h), reserve, wait, launch, blend, defer the order build
-int draw_mega(DevFx* fx, DevTex* target, pt::TraceArgs& a, bool mesh, int gx, int gy)
+// The megakernel draw over gx x gy tiles: plan (pt_plan.h), reserve, wait, launch, blend (or leave the blend to the
+// loop's screenOutput), defer the order build
+// (`wait_prev`: the draw's previousBuffer when its blend may wait for the loop's next draws, else NULL)
+int draw_mega(DevFx* fx, DevTex* target, pt::TraceArgs& a, bool mesh, int gx, int gy, DevTex* wait_prev)
 {
     Dev* c = fx->ctx;
     // ---- plan. Late-bounce compaction and the frames in flight first (cont_decide).
@@ -899,7 +959,12 @@ int draw_mega(DevFx* fx, DevTex* target, pt::TraceArgs& a, bool mesh, int gx, in
     // ---- blend: the history half of main() on the main stream, where the copy / output draws that read the
     // accumulation follow
     pt::BlendArgs b{ a.width, a.height, a.num_parts, a.part, a.frame, a.moving, a.rad, a.prev, a.out, a.cont_count, a.cont_bins };
-    HIPCHK(c, pt_launch_blend(&b, gy, c->stream, g.one_wave ? c->k.main_waves : 0));
+    if (wait_prev) {   // ... or folded into the screenOutput that follows the loop's screenCopy (render_output)
+        c->pending_blend = { b, gy, g.one_wave ? c->k.main_waves : 0 };
+        c->plan.defer_blend(target, wait_prev);
+    } else {
+        HIPCHK(c, pt_launch_blend(&b, gy, c->stream, g.one_wave ? c->k.main_waves : 0));
+    }
     // ---- feature targets: the staged G-buffer folded right after, on the main stream too, so folds keep the draws' order
     // (the moments target alone stages nothing: the fold reads the set's rad, which every pt_trace variant writes.
     // The set's next writer, draw k + sets, waits for the mark draw k + 1 records on this stream, after this fold.)
@@ -920,37 +985,46 @@ int draw_mega(DevFx* fx, DevTex* target, pt::TraceArgs& a, bool mesh, int gx, in
     return PT_OK;
 }
 
+// Whether the blend of a megakernel draw of `target` may wait for the loop's screenCopy and screenOutput to take it
+// along (pt::MainPlan): a whole-frame draw whose two textures nothing but this API can read or write. Off for
+// caller-provided memory (the caller may read it without a call), a partitioned frame (the parts exchange halo rows
+// between the blend and the output), counting draws, experiment builds, and a draw that samples another render target.
+bool blend_may_wait(const DevFx* fx, const DevTex* target, const DevTex* prev)
+{
+    const Dev* c = fx->ctx;
+    if (!c->k.fuse_blend || c->backend != PT_BACKEND_MEGAKERNEL || c->counting || PT_SECPROF_BUILD) return false;
+    if (c->num_parts != 1 || c->output_partition) return false;
+    // the fused pass is one-wave workgroups, what the main stream's passes are for frames of up to 8192 tiles; above
+    // (4K), 256-thread workgroups lost to the two passes (dragon stand-in 4K -2.4 to -3 %)
+    if (c->k.main_waves <= 0 || !target || !pt::MegaGrid::one_wave_tiles((size_t)((target->w + pt::kTile - 1) / pt::kTile) * bands_owned(c, target->h)))
+        return false;
+    if (!target || !prev || target == prev || target->d == prev->d || target->kind != TEX_RT || prev->kind != TEX_RT) return false;
+    if (target->external || prev->external || target->exposed || prev->exposed) return false;
+    for (const auto& kv : fx->samplers)
+        if (kv.second && kv.second->kind == TEX_RT && kv.first != "previousBuffer") return false;
+    return true;
+}
+
 int render_trace(DevFx* fx, DevTex* target)
 {
     Dev* c = fx->ctx;
+    // what the draws before left deferred: a waiting blend runs (its buffer set's consumer, before this draw's mark),
+    // and a stale texture is brought up to date unless it is one of this draw's pair and the draw's blend may wait
+    DevTex* const prev = sampler(fx, "previousBuffer");
+    const bool wait = blend_may_wait(fx, target, prev);
+    {
+        pt::MainPlan::Ops ops;
+        c->plan.before_trace(target, prev, wait, ops);
+        if (int rc = run_deferred(c, ops)) return rc;
+    }
     if (int rc = flush_order(c)) return rc;   // the last draw's order (before slab[LPT] could be reallocated)
     pt::TraceArgs a;
     bool mesh = false;
     if (int rc = trace_args(fx, target, a, mesh)) return rc;
     if (int rc = feature_check(fx, target)) return rc;
     const int gx = (target->w + pt::kTile - 1) / pt::kTile, gy = bands_owned(c, target->h);
-    return c->backend == PT_BACKEND_MEGAKERNEL && gy > 0 ? draw_mega(fx, target, a, mesh, gx, gy)
-                                                         : draw_queued(fx, target, a, mesh, gx, gy);
-}
-
-int launch_copy(Dev* c, DevTex* src, DevTex* dst, int num_parts, int part)
-{
-    pt::CopyArgs a{ dst->w, dst->h, num_parts, part, (const float4*)src->d, (float4*)dst->d };
-    const int gx = (dst->w + 255) / 256, gy = pt::bands_owned(dst->h, num_parts, part);
-    if (gy > 0) HIPCHK(c, pt_launch_copy(&a, gx, gy, c->stream));
-    return PT_OK;
-}
-
-// run a deferred screenCopy now, as its own kernel (timed as a screenCopy draw)
-int flush_copy(Dev* c)
-{
-    if (!c->pending_copy.on) return PT_OK;
-    c->pending_copy.on = false;
-    int rc = begin_draw(c, PT_PROG_SCREEN_COPY);
-    if (rc) return rc;
-    rc = launch_copy(c, c->pending_copy.src, c->pending_copy.dst, c->pending_copy.num_parts, c->pending_copy.part);
-    if (rc) return rc;
-    return end_draw(c, PT_PROG_SCREEN_COPY);
+    if (c->backend == PT_BACKEND_MEGAKERNEL && gy > 0) return draw_mega(fx, target, a, mesh, gx, gy, wait ? prev : nullptr);
+    return draw_queued(fx, target, a, mesh, gx, gy);
 }
 
 int render_copy(DevFx* fx, DevTex* target)
@@ -960,12 +1034,12 @@ int render_copy(DevFx* fx, DevTex* target)
     if (!target || target->kind != TEX_RT) return fail(c, PT_ERR_ARG, "screenCopy needs a render target");
     if (!src || src->kind == TEX_U8 || src->w != target->w || src->h != target->h)
         return fail(c, PT_ERR_STATE, "pathTracedImageBuffer must be an RGBA32F texture of the target's size");
-    int rc = flush_copy(c);
-    if (rc) return rc;
     // deferred: the render loop's next draw is screenOutput of the same source, which writes the
-    // copy target in the same pass (render_output); any other use flushes it first (flush_copy)
-    if (src != target) c->pending_copy = { true, src, target, c->num_parts, c->part };
-    return PT_OK;
+    // copy target in the same pass, or with a waiting blend leaves it stale (render_output); any other
+    // use flushes it first (flush_deferred)
+    pt::MainPlan::Ops ops;
+    c->plan.copy(src, target, c->num_parts, c->part, ops);
+    return run_deferred(c, ops);
 }
 
 int render_output(DevFx* fx, DevTex* target)
@@ -982,14 +1056,6 @@ int render_output(DevFx* fx, DevTex* target)
     a.exposure = uf(fx, "uToneMappingExposure");
     a.num_parts = c->output_partition ? c->num_parts : 1;
     a.part = c->output_partition ? c->part : 0;
-    // fuse the deferred screenCopy when this pass covers exactly its texels: same source, same
-    // frame size, same bands, and the copy target is not this pass's output
-    const auto& pc = c->pending_copy;
-    const int ow = target ? target->w : (c->cw || c->ch ? c->cw : acc->w), oh = target ? target->h : (c->cw || c->ch ? c->ch : acc->h);
-    const bool fuse = pc.on && pc.src == acc && pc.dst != target && ow == acc->w && oh == acc->h &&
-                      pc.num_parts == a.num_parts && (pc.num_parts == 1 || pc.part == a.part);
-    if (fuse) { a.copy_dst = (float4*)pc.dst->d; c->pending_copy.on = false; }
-    else { int frc = flush_copy(c); if (frc) return frc; }
     if (target) {
         if (target->kind != TEX_RT) return fail(c, PT_ERR_ARG, "screenOutput target must be a render target or the canvas");
         a.width = target->w; a.height = target->h; a.out_f = (float4*)target->d;
@@ -1000,6 +1066,18 @@ int render_output(DevFx* fx, DevTex* target)
         }
         a.width = c->cw; a.height = c->ch; a.canvas = c->canvas;
     }
+    // fuse the deferred screenCopy when this pass covers exactly its texels: same source, same
+    // frame size, same bands, and the copy target is not this pass's output; and the draw's waiting blend
+    // with it when the pass covers the whole texture (pt::MainPlan::output)
+    const auto& pc = c->plan.stale;
+    const bool same = a.width == acc->w && a.height == acc->h;
+    pt::MainPlan::Ops ops;
+    c->plan.output(acc, target, same && a.num_parts == 1 && c->num_parts == 1,
+                   same && pc.num_parts == a.num_parts && (pc.num_parts == 1 || pc.part == a.part), ops);
+    const pt::MainPlan::Op pass = ops.op[--ops.n];   // the pass itself is the last one: OUTPUT or FUSED
+    if (int frc = run_deferred(c, ops)) return frc;
+    const bool fused = pass.kind == pt::MainPlan::FUSED;
+    if (!fused && pass.dst) a.copy_dst = (float4*)((DevTex*)pass.dst)->d;
     // the order build rides along only up to 32768 tiles (4K): beyond, the block's 256 threads would
     // loop over memory and outlast the pass, so it runs alone first (1024 threads)
     if (c->order_pending && c->pending_order.ntiles > pt::kOrderHeld * 256u)
@@ -1015,7 +1093,18 @@ int render_output(DevFx* fx, DevTex* target)
         // ~2 MP, and a rank's share of 4K), else the 4-wave blocks with a 256-thread order build
         const unsigned tiles = (unsigned)((a.width + 15) / 16) * (unsigned)pt::bands_owned(a.height, a.num_parts, a.part);   // (as pt_launch_output's grid)
         const bool one = std::max(tiles, a.ob.ntiles) <= pt::kOrderHeld * 64u;   // (ob.ntiles 0: no order build)
-        HIPCHK(c, pt_launch_output(&a, c->stream, one ? c->k.main_waves : 0));
+        if (fused) {   // history + radiance -> the accumulation and this pass's pixels at once
+            pt::FusedArgs fa{ a, c->pending_blend.b };
+            fa.o.acc = nullptr;
+            fa.b.prev = (const float4*)((const DevTex*)pass.src)->d;
+            fa.b.out = (float4*)((DevTex*)pass.dst)->d;
+            HIPCHK(c, pt_launch_output_fused(&fa, c->stream));
+            c->fused_passes++;
+        } else {
+            HIPCHK(c, pt_launch_output(&a, c->stream, one ? c->k.main_waves : 0));
+        }
+    } else if (fused) {
+        return fail(c, PT_ERR_STATE, "screenOutput: empty pass with a blend waiting");
     }
     return end_draw(c, fx->prog);
 }
@@ -1110,7 +1199,7 @@ void dev_ctx_destroy(Dev* c)
 {
     if (!c) return;
     hipSetDevice(c->device);
-    c->pending_copy.on = false;   // nothing can observe its target any more
+    c->plan = pt::MainPlan();     // nothing can observe the loop's textures any more
     c->order_pending = false;     // ... nor a next draw the order
     if (c->stream) hipStreamSynchronize(c->stream);
     for (int p = 0; p < Dev::kDepthMax; p++)   // (pt_trace on the side streams reads and writes the order arrays)
@@ -1145,7 +1234,7 @@ int dev_sync(Dev* c)
 {
     if (!c) return PT_ERR_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = flush_copy(c)) return rc;
+    if (int rc = flush_deferred(c)) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     unsigned flags = 0;
     HIPCHK(c, hipMemcpy(&flags, c->d_err, sizeof(flags), hipMemcpyDeviceToHost));
@@ -1194,6 +1283,10 @@ int dev_canvas_wrap(Dev* c, int w, int h, void* ptr)
 int dev_set_output_partition(Dev* c, int enable)
 {
     if (!c) return PT_ERR_ARG;
+    if (c->output_partition != (enable != 0)) {
+        HIPCHK(c, hipSetDevice(c->device));
+        if (int rc = flush_deferred(c)) return rc;
+    }
     c->output_partition = enable != 0;
     return PT_OK;
 }
@@ -1299,7 +1392,7 @@ int dev_render_target_resize(DevTex* t, int w, int h)
     Dev* c = t->ctx;
     if (w == t->w && h == t->h) return PT_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = flush_copy(c)) return rc;
+    if (int rc = flush_deferred(c)) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (t->d) HIPCHK(c, hipFree(t->d));
     t->d = nullptr;
@@ -1322,7 +1415,9 @@ void dev_texture_destroy(DevTex* t)
     if (!t) return;
     Dev* c = t->ctx;
     hipSetDevice(c->device);
-    if (c->pending_copy.on && (c->pending_copy.src == t || c->pending_copy.dst == t)) flush_copy(c);
+    const pt::MainPlan& pl = c->plan;
+    if ((pl.stale.on && (pl.stale.src == t || pl.stale.dst == t)) || (pl.blend.on && (pl.blend.target == t || pl.blend.prev == t)))
+        flush_deferred(c);
     for (auto* fx : c->effects)
         for (auto& kv : fx->samplers)
             if (kv.second == t) kv.second = nullptr;
@@ -1343,10 +1438,8 @@ int dev_render(DevFx* fx, DevTex* target)
     Dev* c = fx->ctx;
     if (target && target->ctx != c) return fail(c, PT_ERR_ARG, "target belongs to another context");
     HIPCHK(c, hipSetDevice(c->device));
-    if (fx->prog != PT_PROG_SCREEN_OUTPUT && fx->prog != PT_PROG_SCREEN_COPY) {
-        int rc = flush_copy(c);
-        if (rc) return rc;
-    }
+    // (every draw settles what is deferred before it: the loop's three by pt::MainPlan's rules - render_trace,
+    // render_copy, render_output - and any other by running it all)
     switch (fx->prog) {
     case PT_PROG_CORNELL:
     case PT_PROG_QUADRIC:
@@ -1356,7 +1449,9 @@ int dev_render(DevFx* fx, DevTex* target)
     case PT_PROG_GLTF: return render_trace(fx, target);
     case PT_PROG_SCREEN_COPY: return render_copy(fx, target);
     case PT_PROG_SCREEN_OUTPUT: return render_output(fx, target);
-    default: return fail(c, PT_ERR_UNSUPPORTED, "program recognised but not implemented in this build");
+    default:
+        if (int rc = flush_deferred(c)) return rc;
+        return fail(c, PT_ERR_UNSUPPORTED, "program recognised but not implemented in this build");
     }
 }
 
@@ -1364,7 +1459,7 @@ int dev_read_pixels(Dev* c, const DevTex* t, void* dst, size_t bytes)
 {
     if (!c || !dst) return PT_ERR_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = flush_copy(c)) return rc;
+    if (int rc = flush_deferred(c)) return rc;
     const void* src = t ? t->d : (const void*)c->canvas;
     size_t need = t ? t->bytes : (size_t)c->cw * c->ch * sizeof(uchar4);
     if (bytes < need) return fail(c, PT_ERR_ARG, "destination too small");
@@ -1377,7 +1472,7 @@ int dev_write_pixels(Dev* c, DevTex* t, const void* src, size_t bytes)
 {
     if (!c || !t || !src || bytes != t->bytes) return PT_ERR_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = flush_copy(c)) return rc;
+    if (int rc = flush_deferred(c)) return rc;
     HIPCHK(c, hipMemcpyAsync(t->d, src, bytes, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     t->gen++;
@@ -1388,7 +1483,7 @@ int dev_set_stream(Dev* c, void* stream)
 {
     if (!c) return PT_ERR_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = flush_copy(c)) return rc;
+    if (int rc = flush_deferred(c)) return rc;
     if (int rc = flush_order(c)) return rc;        // on the stream its draw ran on
     HIPCHK(c, hipStreamSynchronize(c->stream));   // work already queued finishes first
     c->stream = stream ? (hipStream_t)stream : c->own_stream;
@@ -1400,6 +1495,8 @@ int dev_set_backend(Dev* c, int backend)
 {
     if (!c || (backend != PT_BACKEND_MEGAKERNEL && backend != PT_BACKEND_WAVEFRONT && backend != PT_BACKEND_PERSISTENT))
         return PT_ERR_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = flush_deferred(c)) return rc;
     c->backend = backend;
     return PT_OK;
 }
@@ -1416,12 +1513,27 @@ int dev_bvh_layout_used(Dev* c) { return c ? c->bvh_used : PT_ERR_ARG; }
 int dev_set_row_partition(Dev* c, int num_parts, int part)
 {
     if (!c || num_parts < 1 || part < 0 || part >= num_parts) return PT_ERR_ARG;
+    if (num_parts != c->num_parts || part != c->part) {   // (a waiting blend and a stale texture are whole-frame passes)
+        HIPCHK(c, hipSetDevice(c->device));
+        if (int rc = flush_deferred(c)) return rc;
+    }
     c->num_parts = num_parts;
     c->part = part;
     return PT_OK;
 }
 
 void* dev_texture_device_ptr(DevTex* t) { return t ? t->d : nullptr; }
+
+// the texture's device pointer goes to the caller, who may from now on read or write the texels on the context's
+// stream without a call: everything deferred runs, and no blend of a draw with this texture waits again
+int dev_texture_expose(DevTex* t)
+{
+    if (!t) return PT_ERR_ARG;
+    Dev* c = t->ctx;
+    t->exposed = true;
+    HIPCHK(c, hipSetDevice(c->device));
+    return flush_deferred(c);
+}
 
 int dev_last_render_ms(Dev* c, int prog, float* ms)
 {
@@ -1450,7 +1562,7 @@ int dev_timing_end(Dev* c, int prog, double* total_ms, int* launches)
 {
     if (!c || !total_ms || !launches) return PT_ERR_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = flush_copy(c)) return rc;
+    if (int rc = flush_deferred(c)) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->window = false;   // the window is closed; its draws stay readable by further dev_timing_end calls
     double t = 0.0;
@@ -1471,7 +1583,7 @@ int dev_timing_latency(Dev* c, int prog, float* ms, int cap, int* n)
 {
     if (!c || !n || cap < 0 || (cap && !ms)) return PT_ERR_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = flush_copy(c)) return rc;
+    if (int rc = flush_deferred(c)) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->window = false;
     // each bracketed draw of `prog` with the next bracketed screenOutput draw: the same frame's, as long as
@@ -1494,6 +1606,10 @@ int dev_timing_latency(Dev* c, int prog, float* ms, int cap, int* n)
 int dev_set_counting(Dev* c, int enable)
 {
     if (!c) return PT_ERR_ARG;
+    if (c->counting != (enable != 0)) {
+        HIPCHK(c, hipSetDevice(c->device));
+        if (int rc = flush_deferred(c)) return rc;
+    }
     c->counting = enable != 0;
     return PT_OK;
 }
@@ -1520,6 +1636,7 @@ int dev_queue_stats(Dev* c, uint32_t out[16])
     if (!c || !out) return PT_ERR_ARG;
     std::memset(out, 0, 16 * sizeof(uint32_t));
     HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = flush_blend(c)) return rc;
     if (int rc = flush_order(c)) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const int p = c->ov.next().set;   // the tiles the next megakernel draw of the same grid splits
@@ -1543,11 +1660,20 @@ int dev_queue_stats(Dev* c, uint32_t out[16])
     return PT_OK;
 }
 
+int dev_fuse_stats(Dev* c, uint64_t out[2])
+{
+    if (!c || !out) return PT_ERR_ARG;
+    out[0] = c->fused_passes;
+    out[1] = c->stale_copies;
+    return PT_OK;
+}
+
 int dev_cont_stats(Dev* c, uint64_t out[2])
 {
     if (!c || !out) return PT_ERR_ARG;
     out[0] = out[1] = 0;
     HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = flush_blend(c)) return rc;       // (a waiting blend: its pass keeps the draw's total)
     HIPCHK(c, hipStreamSynchronize(c->stream));   // (every draw's pt_blend, which keeps the totals, is on it)
     uint64_t stored = 0;
     if (int rc = cont_totals(c, &stored)) return rc;
@@ -1600,7 +1726,7 @@ int dev_denoise(Dev* c, const DevTex* beauty, const DevTex* normal_id, const Dev
         return fail(c, PT_ERR_ARG, "pt_denoise: the sigmas must be finite and > 0");
     if (demodulate != 0 && demodulate != 1) return fail(c, PT_ERR_ARG, "pt_denoise: demodulate must be 0 or 1");
     HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = flush_copy(c)) return rc;
+    if (int rc = flush_deferred(c)) return rc;
     const size_t pixels = (size_t)dst->w * dst->h;
     DevMem& mem = c->slab[Dev::DENOISE];
     if (pixels > mem.size)
@@ -1641,7 +1767,7 @@ int dev_denoise_variance(Dev* c, const DevTex* beauty, const DevTex* normal_id, 
         return fail(c, PT_ERR_ARG, "pt_denoise_variance: the sigmas must be finite and > 0");
     if (demodulate != 0 && demodulate != 1) return fail(c, PT_ERR_ARG, "pt_denoise_variance: demodulate must be 0 or 1");
     HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = flush_copy(c)) return rc;
+    if (int rc = flush_deferred(c)) return rc;
     const size_t pixels = (size_t)dst->w * dst->h;
     DevMem& mem = c->slab[Dev::DENOISE_VAR];
     if (pixels > mem.size)
@@ -1685,7 +1811,7 @@ int dev_canvas_encode_jpeg(Dev* c, int quality, int subsampling, int optimize, u
     if (c->cw > 65535 || c->ch > 65535)   // (SOF0's 16-bit fields; the DRI field alone would allow 65535 x 8 columns)
         return fail(c, PT_ERR_ARG, "pt_canvas_encode_jpeg: a JPEG is at most 65535 x 65535");
     HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = flush_copy(c)) return rc;
+    if (int rc = flush_deferred(c)) return rc;
     const int hs = ptj::sampling_h(subsampling), vs = ptj::sampling_v(subsampling);
     const pt::JpegLayout L(c->cw, c->ch, hs, vs, optimize ? pt::kJpegOptBlockBytes : pt::kJpegBlockBytes);
     DevMem& mem = c->slab[Dev::JPEG];
@@ -1787,5 +1913,5 @@ void* dev_canvas_ptr(Dev* c) { return c->canvas; }
 int dev_flush(Dev* c)
 {
     HIPCHK(c, hipSetDevice(c->device));
-    return flush_copy(c);
+    return flush_deferred(c);
 }

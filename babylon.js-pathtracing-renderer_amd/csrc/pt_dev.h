@@ -55,6 +55,7 @@ int dev_set_bvh_layout(Dev* c, int layout);
 int dev_bvh_layout_used(Dev* c);
 int dev_set_row_partition(Dev* c, int num_parts, int part);
 void* dev_texture_device_ptr(DevTex* t);
+int dev_texture_expose(DevTex* t);
 int dev_last_render_ms(Dev* c, int prog, float* ms);
 int dev_timing_begin(Dev* c);
 int dev_timing_end(Dev* c, int prog, double* total_ms, int* launches);
@@ -63,6 +64,7 @@ int dev_read_counters(Dev* c, uint64_t out[PT_NUM_COUNTERS]);
 int dev_reset_counters(Dev* c);
 int dev_timing_latency(Dev* c, int prog, float* ms, int cap, int* n);
 int dev_queue_stats(Dev* c, uint32_t out[16]);
+int dev_fuse_stats(Dev* c, uint64_t out[2]);
 int dev_cont_stats(Dev* c, uint64_t out[2]);
 int dev_set_feature_targets(DevFx* fx, DevTex* normal_id, DevTex* albedo_weight);
 int dev_denoise(Dev* c, const DevTex* beauty, const DevTex* normal_id, const DevTex* albedo_weight, DevTex* dst,

@@ -588,7 +588,12 @@ int pt_set_bvh_layout(pt_ctx* c, int layout)
 
 int pt_bvh_layout_used(pt_ctx* c) { return c ? dev_bvh_layout_used(c->parts[0]) : PT_ERR_ARG; }
 
-void* pt_texture_device_ptr(pt_texture* t) { return t ? dev_texture_device_ptr(t->sub[0]) : nullptr; }
+void* pt_texture_device_ptr(pt_texture* t)
+{
+    if (!t) return nullptr;
+    for (DevTex* s : t->sub) dev_texture_expose(s);   // (the caller may now read the texels without a call)
+    return dev_texture_device_ptr(t->sub[0]);
+}
 
 int pt_last_render_ms(pt_ctx* c, int prog, float* ms)
 {
@@ -675,6 +680,12 @@ int pt_cont_stats(pt_ctx* c, uint64_t out[2])
 {
     if (!c || !out) return PT_ERR_ARG;
     return sum_parts<2>(c, out, dev_cont_stats);
+}
+
+int pt_fuse_stats(pt_ctx* c, uint64_t out[2])
+{
+    if (!c || !out) return PT_ERR_ARG;
+    return sum_parts<2>(c, out, dev_fuse_stats);
 }
 
 int pt_set_feature_targets(pt_effect* fx, pt_texture* normal_id, pt_texture* albedo_weight)

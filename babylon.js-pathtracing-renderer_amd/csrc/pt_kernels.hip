@@ -9,6 +9,7 @@
 //                         luminance moments into the moments target.
 //   pt_output             screenOutput (js/PathTracingCommon.js:19-309): 5x5 / 3x3 edge-aware
 //                         filter, 1/N, Reinhard, gamma 0.4545, unorm8.
+//   pt_output_f1          the render loop's history blend, screenCopy and screenOutput as one pass (FusedArgs).
 //   pt_math_probe_kernel  device self-test of the pinned built-ins.
 //
 // Mapping onto CDNA4:
@@ -321,12 +322,17 @@ __global__ __launch_bounds__(64) void pt_feature_fold(FoldArgs a, int units_x, i
 // tap at integer position (x, y) = pixel + (dx, dy) (js/PathTracingCommon.js:44-72): ivec2() of a
 // float truncates toward zero, so position -1 (fragment coordinate -0.5) reads texel 0 and -2
 // (-1.5) is outside the texture: 0 (pinned)
-PT_D float4 accAt(const OutputArgs& a, int x, int y)
+PT_D long long accIndex(const OutputArgs& a, int x, int y)   // (-1: outside)
 {
     x = (int)((float)x + 0.5f);
     y = (int)((float)y + 0.5f);
-    if (x < 0 || y < 0 || x >= a.acc_w || y >= a.acc_h) return make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    return a.acc[(long long)y * a.acc_w + x];
+    if (x < 0 || y < 0 || x >= a.acc_w || y >= a.acc_h) return -1;
+    return (long long)y * a.acc_w + x;
+}
+PT_D float4 accAt(const OutputArgs& a, int x, int y)
+{
+    const long long i = accIndex(a, x, y);
+    return i < 0 ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : a.acc[i];
 }
 
 // screenOutput of pixel (x, y) from its tile's 20x20 neighbourhood staged in LDS (lx, ly: the
@@ -484,6 +490,77 @@ __global__ __launch_bounds__(64) void pt_output_w(OutputArgs a, int tiles_x, int
         if (tn < ntiles) store(cur ^ 1);
         __syncthreads();
         t = tn; x0 = nx0; y0 = ny0;
+    }
+}
+
+// ---- the pending blend of a megakernel draw folded into screenOutput (FusedArgs; the host fuses only the render
+// loop's own three draws: pt_plan.h MainPlan). Staged texel k of the tile at (x0, y0) is historyBlend of the history
+// and the radiance at the texel accAt reads - blendRows' function on blendRows' inputs, hence its bits; a halo texel
+// is formed again by each neighbouring tile, to the same bits.
+PT_D void fusedLoad(const FusedArgs& fa, int k, int x0, int y0, float4& h, float4& r)
+{
+    const long long i = accIndex(fa.o, x0 + k % 20 - 2, y0 + k / 20 - 2);
+    if (i >= 0) { h = fa.b.prev[i]; r = fa.b.rad[i]; }
+}
+// ... blended; the tile's own 16x16 texels (each staged by exactly one tile) go to the accumulation
+PT_D float4 fusedTexel(const FusedArgs& fa, int k, int x0, int y0, const float4& h, const float4& r)
+{
+    const int kx = k % 20, ky = k / 20;
+    const long long i = accIndex(fa.o, x0 + kx - 2, y0 + ky - 2);
+    if (i < 0) return make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    const float4 v = historyBlend(h, mk(r.x, r.y, r.z), r.w, fa.b.frame, fa.b.moving);
+    if (kx >= 2 && kx < 18 && ky >= 2 && ky < 18) fa.b.out[i] = v;
+    return v;
+}
+// the first workgroup takes over what pt_blend's does for the draw's buffer set, in its order
+PT_D void fusedSetReset(const BlendArgs& b)
+{
+    if (blockIdx.x != 0) return;
+    if (b.cont_count && threadIdx.x < 2) contCountReset(b.cont_count);
+    if (b.cont_bins)
+        for (int i = threadIdx.x; i < kSortBins; i += 64) b.cont_bins[i] = 0u;
+}
+
+// One 16x16 tile per one-wave workgroup (see pt_blend_w): each lane 7 of the tile's 400 texels and 4 of its pixels.
+// No tile follows in a workgroup, so nothing is prefetched: one tile buffer in LDS instead of pt_output_w's two and
+// no raw texels held in registers across the shading (110 VGPRs and 6.9 KB against 156 and 13.3 KB). Beside the
+// overlapped frames' path tracing a workgroup costs the frame what it holds while it runs:
+// workgroups that walk several tiles with the next one's history and radiance prefetched, as pt_output_w's can,
+// lost 1 % to the two passes, this form gains 2 %. For frames of up to 8192 tiles; above, 256-thread workgroups
+// (either form) lost at 4K, and the host keeps the two passes there (pt_capi.cpp blend_may_wait).
+__global__ __launch_bounds__(64) void pt_output_f1(FusedArgs fa, int tiles_x, int ntiles)
+{
+    const OutputArgs& a = fa.o;
+    __shared__ float4 tile[20 * 20];
+    const int tid = threadIdx.x;
+    const int lx = tid & 15, ly = tid >> 4;
+    fusedSetReset(fa.b);
+    int t = (int)blockIdx.x;
+    if (a.ob.cost) {   // block 0: the next megakernel draw's order (pt_order_build), beside the tiles
+        if (t == 0) {
+            orderBuild(a.ob);
+            return;
+        }
+        t--;
+    }
+    if (t >= ntiles) return;
+    const int x0 = (t % tiles_x) * 16, y0 = ((t / tiles_x) * a.num_parts + a.part) * 16;
+    float4 h[7], r[7];
+#pragma unroll
+    for (int i = 0; i < 7; i++) {
+        const int k = tid + 64 * i;
+        if (k < 400) fusedLoad(fa, k, x0, y0, h[i], r[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < 7; i++) {
+        const int k = tid + 64 * i;
+        if (k < 400) tile[k] = fusedTexel(fa, k, x0, y0, h[i], r[i]);
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int j = 0; j < 4; j++) {
+        const int x = x0 + lx, y = y0 + ly + 4 * j;
+        if (x < a.width && y < a.height) outputPixel(a, tile, lx, ly + 4 * j, x, y);
     }
 }
 
@@ -709,6 +786,18 @@ hipError_t pt_launch_output(const pt::OutputArgs* a, hipStream_t s, int waves)
     const int blocks = ntiles / 4 < 4096 ? 4096 : ntiles / 4 > 8192 ? 8192 : ntiles / 4;
     hipLaunchKernelGGL(pt::pt_output, dim3((ntiles < blocks ? ntiles : blocks) + (a->ob.cost ? 1 : 0)), dim3(256), 0, s, *a,
                        (int)grid.x, ntiles);
+    return hipGetLastError();
+}
+
+// screenOutput with the draw's pending blend folded in: a one-wave workgroup per tile. The host fuses only an
+// output that covers the whole accumulation, so there is always a band.
+hipError_t pt_launch_output_fused(const pt::FusedArgs* fa, hipStream_t s)
+{
+    const pt::OutputArgs* a = &fa->o;
+    dim3 grid((a->width + 15) / 16, pt::bands_owned(a->height, a->num_parts, a->part));
+    if (grid.y == 0 || fa->b.prev == fa->b.out) return hipErrorInvalidValue;
+    const int ntiles = (int)(grid.x * grid.y);
+    hipLaunchKernelGGL(pt::pt_output_f1, dim3(ntiles + (a->ob.cost ? 1 : 0)), dim3(64), 0, s, *fa, (int)grid.x, ntiles);
     return hipGetLastError();
 }
 

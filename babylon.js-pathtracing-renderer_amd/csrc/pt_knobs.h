@@ -60,6 +60,10 @@ struct Knobs {
     int lpt_flat = 6;
     int lpt_flat_tiles = 8192;    // (PT_LPT_FLAT_TILES) ... for frames of more than this many tiles
     int fuse_order = 1;           // (PT_FUSE_ORDER) the order build rides along with the next screenOutput; 0: alone
+    // (PT_FUSE_BLEND) a megakernel draw's blend waits for the render loop's screenCopy and screenOutput and runs
+    // folded into the output pass (pt_output_f1; frames of up to 8192 tiles), the copy target left stale (pt_plan.h MainPlan); 0: pt_blend
+    // right after the draw, the copy riding along with the output
+    int fuse_blend = 1;
     // (PT_MAIN_WAVES) pt_blend / pt_output as up to this many one-wave workgroups (0: 4-wave blocks) for frames
     // of up to 8192 tiles (r05bi: dragon stand-in 1080p +2 %, helmet +3 %; at 4K -4 %)
     int main_waves = 16384;
@@ -123,6 +127,7 @@ inline void read_knobs(Knobs& k, const char* (*get)(const char*) = knob_env)
     if (const char* v = get("PT_OVERLAP_DEPTH")) { k.depth = knob_int(v, 2, kDepthMax); k.depth_env = true; }
     if (const char* v = get("PT_CONT_WAVES")) { k.cont_waves = knob_int(v, 1, INT_MAX); k.cont_waves_env = true; }
     if (const char* v = get("PT_CONT_SORT_GRID")) { k.cont_grid_bits = knob_int(v, 1, 3); k.cont_grid_env = true; }
+    if (const char* v = get("PT_FUSE_BLEND")) k.fuse_blend = knob_int(v, LONG_MIN, LONG_MAX) != 0;   // a switch, as the table's
     if (const char* v = get("PT_SPLIT_ALWAYS")) k.split_dominance = knob_int(v, INT_MIN, INT_MAX) ? 0 : 8;
     if (const char* v = get("PT_BVH_LAYOUT"))   // reference | pairs | trail: the context's initial walk
         k.bvh_layout = !std::strcmp(v, "trail") ? 2 : !std::strcmp(v, "reference") ? 0 : 1;

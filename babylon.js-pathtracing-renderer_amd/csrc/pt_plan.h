@@ -273,6 +273,109 @@ struct Overlap {
     }
 };
 
+// The main stream's deferred passes (pt_capi.cpp issues the kernels this decides). The render loop draws, per frame,
+//   path tracing into A with previousBuffer B  ->  screenCopy A -> B  ->  screenOutput of A,
+// so after every frame A and B hold the same bits and B is only ever read as the next frame's history. Two things
+// wait here for the draw that follows them:
+//   * the draw's blend (history + radiance -> A; pt_blend), pending from the megakernel draw (`blend`);
+//   * a screenCopy (`stale`): dst's texels are to be src's, and dst is stale until pt_copy has run.
+// When the next two draws are the loop's own - the screenCopy of the blend's target to its previousBuffer, then a
+// screenOutput that covers exactly the target's texels - ONE pass blends, shades and writes the accumulation
+// (FUSED). It reads the history with a 2-texel halo, so it must not write the texture it reads: it reads the one
+// that holds the last frame's accumulation (B, or A while B is stale) and writes the other, which leaves the
+// first one stale. The two textures alternate, and in the steady loop no copy ever runs. Every other observation
+// of either texture first runs what is pending, in the order the draws were made: the parent's passes, unchanged.
+// Textures are opaque pointers here; `ops` is what the host launches, in order.
+struct MainPlan {
+    typedef const void* Tex;
+    enum Kind { COPY, BLEND, FUSED, OUTPUT };
+    struct Op {
+        Kind kind;
+        Tex src;   // COPY: source | BLEND: the history | FUSED: the history | OUTPUT: the accumulation
+        Tex dst;   // COPY: target | BLEND: the target  | FUSED: the accumulation written | OUTPUT: a copy riding along, or NULL
+        int num_parts, part;   // COPY: the bands it covers (those of the partition that drew it)
+    };
+    struct Ops {
+        int n = 0;
+        Op op[4];
+        void add(Kind k, Tex s, Tex d, int num_parts = 1, int part = 0) { op[n++] = Op{ k, s, d, num_parts, part }; }
+    };
+    struct { bool on; Tex src, dst; int num_parts, part; } stale = {};
+    struct { bool on, copy_after; Tex target, prev; } blend = {};
+
+    // pt_copy for the stale texture, now
+    void materialise(Ops& o)
+    {
+        if (!stale.on) return;
+        stale.on = false;
+        o.add(COPY, stale.src, stale.dst, stale.num_parts, stale.part);
+    }
+    // the pending blend as pt_blend, in place as the draw asked: its previousBuffer first brought up to date (a stale
+    // target needs nothing: an eligible blend overwrites all of it); the loop's screenCopy, if it came, is then
+    // deferred as it always was
+    void resolve_blend(Ops& o)
+    {
+        if (!blend.on) return;
+        if (stale.on && stale.dst == blend.target) stale.on = false;
+        materialise(o);
+        o.add(BLEND, blend.prev, blend.target);
+        blend.on = false;
+        if (blend.copy_after) stale = { true, blend.target, blend.prev, 1, 0 };
+    }
+    // anything that may read or write a texture, or needs the buffer set's counters: everything pending runs
+    void observe(Ops& o)
+    {
+        resolve_blend(o);
+        materialise(o);
+    }
+    // a path-tracing draw into `target` with `prev` as its history. `eligible`: its blend may wait (a megakernel
+    // draw of a whole internal texture pair, target != prev). The loop's stale texture stays stale.
+    void before_trace(Tex target, Tex prev, bool eligible, Ops& o)
+    {
+        resolve_blend(o);
+        const bool pair = stale.on && ((stale.src == target && stale.dst == prev) || (stale.src == prev && stale.dst == target));
+        if (!(eligible && pair)) materialise(o);
+    }
+    // ... and after it: the blend waits. (Not called: the host ran pt_blend itself, before_trace made prev current.)
+    void defer_blend(Tex target, Tex prev) { blend = { true, false, target, prev }; }
+    // screenCopy src -> dst
+    void copy(Tex src, Tex dst, int num_parts, int part, Ops& o)
+    {
+        if (blend.on && !blend.copy_after && src == blend.target && dst == blend.prev) {
+            blend.copy_after = true;
+            return;
+        }
+        resolve_blend(o);
+        materialise(o);
+        if (src != dst) stale = { true, src, dst, num_parts, part };
+    }
+    // screenOutput of `acc` into `out` (NULL: the canvas). `whole`: it covers exactly acc's texels, unpartitioned
+    // (what FUSED needs); `rides`: the stale copy's bands are this pass's (what a copy riding along needs).
+    void output(Tex acc, Tex out, bool whole, bool rides, Ops& o)
+    {
+        const bool pair = !stale.on || (stale.src == blend.target && stale.dst == blend.prev) ||
+                          (stale.src == blend.prev && stale.dst == blend.target);
+        if (blend.on && blend.copy_after && pair && acc == blend.target && out != blend.target && out != blend.prev && whole) {
+            // the history: the previousBuffer, or the target while the previousBuffer is stale (it then holds the
+            // frame before the last, the target the last)
+            const bool prev_stale = stale.on && stale.dst == blend.prev;
+            const Tex hist = prev_stale ? blend.target : blend.prev, dst = prev_stale ? blend.prev : blend.target;
+            o.add(FUSED, hist, dst);
+            blend.on = false;
+            stale = { true, dst, hist, 1, 0 };
+            return;
+        }
+        resolve_blend(o);
+        if (stale.on && stale.src == acc && stale.dst != out && rides) {
+            stale.on = false;
+            o.add(OUTPUT, acc, stale.dst);
+            return;
+        }
+        materialise(o);
+        o.add(OUTPUT, acc, nullptr);
+    }
+};
+
 // The megakernel's grid for gx x gy tiles. Longest-first: the wave durations of the buffer set's previous draw
 // order this draw's workgroups when it drew the same grid, target and program (`same`); split tiles take 12 more
 // workgroups each, in padding rows. A compacting draw (`cont`) splits none: their 16-lane waves would hand
@@ -290,6 +393,7 @@ struct MegaGrid {
     // early keep the slots full (dragon stand-in 1080p +1.5 %, its 20-frame run +1.7 %, helmet +1.6 %, three
     // rounds, profiles/r06bo_*; uncompacted the bunny lost 1.4 %, and at 4K the flattened order 1.9 %)
     unsigned order_zig;
+    static bool one_wave_tiles(size_t tiles) { return tiles <= kOrderHeld * 64u; }
     MegaGrid(int gx, int gy, bool same, bool cont, const Knobs& k)
     {
         n = (size_t)gx * gy;
@@ -298,7 +402,7 @@ struct MegaGrid {
         const unsigned extra = 4u * kSplitParts - 4u;   // more workgroups per split tile
         gy_grid = gy + (int)((extra * split + 4u * gx - 1) / (4u * gx));
         lanes = (size_t)gx * gy_grid * kBlock;
-        one_wave = n <= kOrderHeld * 64u;
+        one_wave = one_wave_tiles(n);
         order_zig = k.lpt_zig || (cont && k.zig_cont && n <= (size_t)k.lpt_flat_tiles) ? 1u : 0u;
     }
     // pt_cont's one-wave workgroups for a draw of `share` pixels (the sky composite keeps cont_waves: its sky

@@ -411,6 +411,16 @@ static napi_value ContStats(napi_env env, napi_callback_info info)
     for (uint32_t i = 0; i < 2; i++) napi_set_element(env, r, i, num(env, (double)s[i]));
     return r;
 }
+/* pt_fuse_stats(ctx) -> [fused accumulate-and-output passes, screenCopy kernels run for a stale texture] */
+static napi_value FuseStats(napi_env env, napi_callback_info info)
+{
+    napi_value a[MAXARGS], r; if (args(env, info, a, 1) < 0) return NULL;
+    uint64_t s[2] = { 0, 0 };
+    pt_fuse_stats((pt_ctx*)handle(env, a[0]), s);
+    CHECK(napi_create_array_with_length(env, 2, &r));
+    for (uint32_t i = 0; i < 2; i++) napi_set_element(env, r, i, num(env, (double)s[i]));
+    return r;
+}
 /* pt_set_feature_targets(effect, normalId | null, albedoWeight | null) -> status */
 static napi_value SetFeatureTargets(napi_env env, napi_callback_info info)
 {
@@ -520,7 +530,7 @@ static napi_value Init(napi_env env, napi_value exports)
         { "pt_bvh_layout_used", BvhLayoutUsed }, { "pt_set_stream", SetStream }, { "pt_texture_device_ptr", TexDevicePtr },
         { "pt_last_render_ms", LastRenderMs }, { "pt_timing_begin", TimingBegin }, { "pt_timing_end", TimingEnd },
         { "pt_timing_latency", TimingLatency },
-        { "pt_set_counting", SetCounting }, { "pt_read_counters", ReadCounters }, { "pt_reset_counters", ResetCounters }, { "pt_queue_stats", QueueStats }, { "pt_cont_stats", ContStats },
+        { "pt_set_counting", SetCounting }, { "pt_read_counters", ReadCounters }, { "pt_reset_counters", ResetCounters }, { "pt_queue_stats", QueueStats }, { "pt_cont_stats", ContStats }, { "pt_fuse_stats", FuseStats },
         { "pt_set_feature_targets", SetFeatureTargets }, { "pt_denoise", Denoise },
         { "pt_set_moment_target", SetMomentTarget }, { "pt_denoise_variance", DenoiseVariance },
         { "pt_bvh_build", BvhBuild }, { "pt_bvh_build_gpu", BvhBuildGpu },

@@ -41,7 +41,7 @@ SYMBOLS = [
     "pt_render", "pt_read_pixels", "pt_canvas_encode_jpeg", "pt_canvas_encode_jpeg_sub", "pt_canvas_encode_jpeg_opt",
     "pt_write_pixels",
     "pt_set_row_partition", "pt_set_output_partition", "pt_canvas_wrap", "pt_set_backend", "pt_set_bvh_layout", "pt_bvh_layout_used", "pt_set_stream", "pt_texture_device_ptr", "pt_last_render_ms", "pt_timing_begin", "pt_timing_end", "pt_timing_latency",
-    "pt_set_counting", "pt_read_counters", "pt_reset_counters", "pt_queue_stats", "pt_cont_stats", "pt_set_feature_targets", "pt_denoise", "pt_set_moment_target", "pt_denoise_variance", "pt_math_probe", "pt_math_exhaustive", "pt_bvh_build", "pt_bvh_build_gpu", "pt_jpeg_size", "pt_jpeg_decode_rgba8", "pt_version",
+    "pt_set_counting", "pt_read_counters", "pt_reset_counters", "pt_queue_stats", "pt_cont_stats", "pt_fuse_stats", "pt_set_feature_targets", "pt_denoise", "pt_set_moment_target", "pt_denoise_variance", "pt_math_probe", "pt_math_exhaustive", "pt_bvh_build", "pt_bvh_build_gpu", "pt_jpeg_size", "pt_jpeg_decode_rgba8", "pt_version",
 ]
 
 _lib = None
@@ -94,6 +94,7 @@ def lib():
         "pt_math_probe": ([vp, i32, vp, vp, vp, i32], i32),
         "pt_math_exhaustive": ([vp, i32, vp], i32),
         "pt_cont_stats": ([vp, ctypes.POINTER(ctypes.c_uint64)], i32),
+        "pt_fuse_stats": ([vp, ctypes.POINTER(ctypes.c_uint64)], i32),
         "pt_set_feature_targets": ([vp, vp, vp], i32),
         "pt_denoise": ([vp, vp, vp, vp, vp, i32, ctypes.c_float, ctypes.c_float, i32], i32),
         "pt_set_moment_target": ([vp, vp], i32),
@@ -101,6 +102,8 @@ def lib():
         "pt_queue_stats": ([vp, ctypes.POINTER(ctypes.c_uint32)], i32), "pt_version": ([], ctypes.c_char_p),
     }
     for name, (args, res) in sig.items():
+        if name == "pt_fuse_stats" and not hasattr(L, name):
+            continue   # (a libpt.so from before the fused pass, loaded through PT_LIBPT for an A/B)
         fn = getattr(L, name)
         fn.argtypes = args
         fn.restype = res
@@ -261,6 +264,16 @@ class Engine:
                 "frames_in_flight": (int(buf[14]) >> 8) & 0xFF,
                 "compacting_draws": int(buf[14]) >> 16,
                 "compaction_trial_ratio": buf[15] / 1000.0 if buf[15] else None}
+
+    def fuse_stats(self):
+        """(screenOutput draws that took the draw's blend and the screenCopy along as one pass, screenCopy kernels
+        run on their own for a stale copy target) since the engine was created, summed over its parts; no device
+        work. (None, None) from a libpt.so that predates the fused pass."""
+        if not hasattr(lib(), "pt_fuse_stats"):
+            return None, None
+        buf = (ctypes.c_uint64 * 2)()
+        self.check(lib().pt_fuse_stats(self.ctx, buf), "pt_fuse_stats")
+        return int(buf[0]), int(buf[1])
 
     def cont_stats(self):
         """(path records the draws stored for pt_cont, draws that launched pt_cont) since the engine was

@@ -247,7 +247,9 @@ int pt_bvh_layout_used(pt_ctx* ctx);
  * that draws and RCCL collectives are ordered without host syncs); NULL restores the context's own
  * stream. The caller keeps the stream alive while the context uses it. */
 int pt_set_stream(pt_ctx* ctx, void* hip_stream);
-/* Device pointer of a render target's RGBA32F storage (for RCCL collectives from the host). */
+/* Device pointer of a render target's RGBA32F storage (for RCCL collectives from the host). From this call on the
+ * texture counts as caller-visible, as wrapped memory does: everything deferred runs now, and the texels are current
+ * on the context's stream after every draw. */
 void* pt_texture_device_ptr(pt_texture* tex);
 /* Device time of the last pt_render of each program kind, in ms (HIP events on the context
  * stream; requires pt_sync first). Draws are bracketed by events only once this has been called
@@ -292,6 +294,11 @@ int pt_queue_stats(pt_ctx* ctx, uint32_t out[16]);
  * it (not mod 2^16 as in pt_queue_stats); with several parts, summed over them. Each draw's history
  * blend adds its record count to the total as it zeroes it, so the path-tracing kernels pay nothing. */
 int pt_cont_stats(pt_ctx* ctx, uint64_t out[2]);
+/* The render loop's fused pass since the context was created (no device work, no synchronisation): out[0] = the
+ * screenOutput draws that took the path-tracing draw's history blend and the frame's screenCopy along as one pass
+ * (PT_FUSE_BLEND), out[1] = the screenCopy kernels launched on their own, for a copy target that
+ * something had to see up to date; with several parts, summed over them (their frames never fuse: out[0] = 0). */
+int pt_fuse_stats(pt_ctx* ctx, uint64_t out[2]);
 /* Feature buffers: bind (or with NULLs unbind) feature targets to a path-tracing effect. Both are RGBA32F
  * render targets of the draw target's size; either may be NULL (that buffer is then not produced), both NULL
  * turns the feature off. While targets are bound, every pt_render of the effect also folds this draw's
