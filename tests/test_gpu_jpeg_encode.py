@@ -3,7 +3,8 @@ output, tests/test_jpeg_encode.py) over the canvas top-down, no tolerance. The c
 pt_canvas_wrap over a torch uint8 device tensor, so only the last tests render. Sizes are W x H, the smallest at
 which each stage can go wrong: 1x1 and 8x8 (all padding; one block, no restart marker), 17x9 (edge replication on
 both axes, 3x2 MCUs, one RST), 24x80 (ten MCU rows: the RST index wraps past 7), 2056x8 (771 blocks in one restart
-interval, past a 256-wide scan tile)."""
+interval, past a 256-wide scan tile). The loops that only a frame enters (more than 256 MCU rows, a row of thousands of
+blocks, the largest canvas) are tests/test_gpu_jpeg_encode_scale.py's."""
 import ctypes
 import os
 import shutil

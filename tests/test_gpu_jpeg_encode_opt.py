@@ -1,7 +1,9 @@
 """pt_canvas_encode_jpeg_opt on the GPU with optimize = 1: every comparison is bytes == tests/jpeg_enc_opt_ref.py
 (which is libjpeg-turbo's optimize_coding output, tests/test_jpeg_encode_opt.py) over the canvas top-down, no
 tolerance. The canvas content is put there with pt_canvas_wrap over a torch uint8 device tensor, so only the last
-tests render. Sizes are W x H, at most 256 x 256 pixels but for the one-row frames whose row has more than 256 blocks."""
+tests render. Sizes are W x H, at most 256 x 256 pixels but for the one-row frames whose row has more than 256 blocks;
+more than 4096 MCUs (a second pass of pt_jpeg_hist's waves) and more than 256 MCU rows are
+tests/test_gpu_jpeg_encode_scale.py's."""
 import ctypes
 import os
 import shutil

@@ -1,7 +1,8 @@
 """pt_canvas_encode_jpeg_sub on the GPU, 4:2:2 and 4:2:0: every comparison is bytes == tests/jpeg_enc_sub_ref.py
 (which is libjpeg-turbo's output, tests/test_jpeg_encode_sub.py) over the canvas top-down, no tolerance. The canvas
 content is put there with pt_canvas_wrap over a torch uint8 device tensor, so only the last tests render. Sizes are
-W x H, the smallest at which each stage can go wrong, with the dummy Y blocks each must reach (CASES)."""
+W x H, the smallest at which each stage can go wrong, with the dummy Y blocks each must reach (CASES). The loops that
+only a frame enters (more than 256 MCU rows, the largest canvas) are tests/test_gpu_jpeg_encode_scale.py's."""
 import ctypes
 import os
 import shutil
