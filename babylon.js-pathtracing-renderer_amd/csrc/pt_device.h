@@ -659,8 +659,9 @@ PT_D void bvhWalkPairs(const TraceArgs& a, f3 O, f3 D, f3 inv, bool dbl, float c
 // re-tested entry carries the bits it was pushed with, and the walk visits the reference walk's nodes
 // in its order: same hit, same counters (restart descents are no node fetches of the reference's).
 // The host gives it trees of depth <= 28, whose nodes have one parent each (pt_pairs_depth): there
-// at most 27 far children are ever pending, so the reference's stack (stackLevels[28]) never
-// overflows and no push is dropped; other trees keep the stack walk.
+// at most 28 far children are ever pending (one per level of a path to a leaf 28 links below the
+// root), which the reference's stack (stackLevels[28]) holds exactly, so it never overflows and no
+// push is dropped; other trees keep the stack walk.
 struct TrailWalk {
     uint32_t code;             // record to load next
     float hitT;

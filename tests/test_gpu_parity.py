@@ -1,6 +1,8 @@
 """GPU parity: libpt.so (HIP, gfx950) against the CPU oracle on the reference's recorded uniform
 streams. The bar is bit-exact: both sides implement the pinned GLSL semantics,
 so every RGBA32F accumulation texel and every RGBA8 canvas byte must agree exactly.
+The meshes here carry the builder's trees; hand-shaped ones (depth 28 and 29, every level pending,
+tiny trees, shared subtrees, NaN boxes, small BVH textures) are in tests/test_gpu_tree_shapes.py.
 
 Run on an MI355X: python -m pytest tests -m gpu
 """
