@@ -458,6 +458,30 @@ static const float* texel32(const float* base, int64_t n, float idx)
     return base + 4 * (int64_t)idx;
 }
 static float unorm8(uint8_t b) { return (float)b / 255.0f; }
+/* The tap log (ptoracle.h): while a buffer is bound, every bilinear lookup appends a row. One writer only:
+ * pto_path_trace refuses a bound log unless nthreads == 1. */
+static pto_tap* g_tap_rows;
+static int64_t g_tap_cap, g_tap_written, g_tap_dropped;
+static int g_tap_bounce = -1;   /* CalculateRadiance's loop counter while a log is bound; -1 outside a path */
+static void tap_log(int map, float u, float v, int x0, int y0, int x1, int y1)
+{
+    if (g_tap_written < g_tap_cap) {
+        pto_tap* r = &g_tap_rows[g_tap_written++];
+        r->map = map; r->bounce = g_tap_bounce; r->u = u; r->v = v; r->x0 = x0; r->y0 = y0; r->x1 = x1; r->y1 = y1;
+    } else g_tap_dropped++;
+}
+int pto_tap_log_bind(pto_tap* rows, int64_t capacity)
+{
+    if (capacity < 0 || (!rows && capacity != 0)) return -1;
+    g_tap_rows = capacity ? rows : NULL; g_tap_cap = capacity; g_tap_written = 0; g_tap_dropped = 0;
+    return 0;
+}
+void pto_tap_log_count(int64_t* written, int64_t* dropped)
+{
+    if (written) *written = g_tap_written;
+    if (dropped) *dropped = g_tap_dropped;
+}
+
 /* texture(sampler, uv) on an RGBA8 map: LOD 0 bilinear, REPEAT wrap, unorm8 texels */
 static int wrap_texel(float f, int n)
 {
@@ -466,7 +490,7 @@ static int wrap_texel(float f, int n)
     int i = (int)r;
     return i < 0 ? i + n : i;
 }
-static void tex_bilinear(const uint8_t* t, int w, int h, float u, float v, float out[4])
+static void tex_bilinear(int map, const uint8_t* t, int w, int h, float u, float v, float out[4])
 {
     if (!t || w <= 0 || h <= 0) { out[0] = out[1] = out[2] = out[3] = 0.0f; return; }
     float x = u * (float)w - 0.5f, y = v * (float)h - 0.5f;
@@ -474,6 +498,7 @@ static void tex_bilinear(const uint8_t* t, int w, int h, float u, float v, float
     float a = x - fx, b = y - fy;
     int64_t x0 = wrap_texel(fx, w), y0 = wrap_texel(fy, h);
     int64_t x1 = (x0 + 1) % w, y1 = (y0 + 1) % h;
+    if (g_tap_rows) tap_log(map, u, v, (int)x0, (int)y0, (int)x1, (int)y1);
     for (int c = 0; c < 4; c++) {
         float t00 = unorm8(t[4 * (y0 * w + x0) + c]), t10 = unorm8(t[4 * (y0 * w + x1) + c]);
         float t01 = unorm8(t[4 * (y1 * w + x0) + c]), t11 = unorm8(t[4 * (y1 * w + x1) + c]);
@@ -482,7 +507,7 @@ static void tex_bilinear(const uint8_t* t, int w, int h, float u, float v, float
 }
 
 /* texture(sampler, uv) on an RGBA32F map (tHDRTexture): LOD 0 bilinear, REPEAT wrap */
-static void tex_bilinear_f(const float* t, int w, int h, float u, float v, float out[4])
+static void tex_bilinear_f(int map, const float* t, int w, int h, float u, float v, float out[4])
 {
     if (!t || w <= 0 || h <= 0) { out[0] = out[1] = out[2] = out[3] = 0.0f; return; }
     float x = u * (float)w - 0.5f, y = v * (float)h - 0.5f;
@@ -490,11 +515,24 @@ static void tex_bilinear_f(const float* t, int w, int h, float u, float v, float
     float ax = x - fx, by = y - fy;
     int x0 = wrap_texel(fx, w), y0 = wrap_texel(fy, h);
     int x1 = x0 + 1 == w ? 0 : x0 + 1, y1 = y0 + 1 == h ? 0 : y0 + 1;
+    if (g_tap_rows) tap_log(map, u, v, x0, y0, x1, y1);
     const float* t00 = t + 4 * ((size_t)y0 * w + x0);
     const float* t10 = t + 4 * ((size_t)y0 * w + x1);
     const float* t01 = t + 4 * ((size_t)y1 * w + x0);
     const float* t11 = t + 4 * ((size_t)y1 * w + x1);
     for (int k = 0; k < 4; k++) out[k] = g_mix(g_mix(t00[k], t10[k], ax), g_mix(t01[k], t11[k], ax), by);
+}
+
+/* The two samplers on caller-given texels and coordinates (kind 0 RGBA8, 1 RGBA32F): out[4n]. */
+int pto_tex_probe(int kind, const void* texels, int w, int h, const float* u, const float* v, float* out, int n)
+{
+    if ((kind != 0 && kind != 1) || !texels || w <= 0 || h <= 0 || !u || !v || !out || n < 0) return -1;
+    g_tap_bounce = -1;
+    for (int i = 0; i < n; i++) {
+        if (kind == 0) tex_bilinear(PTO_TAP_PROBE, (const uint8_t*)texels, w, h, u[i], v[i], out + 4 * (size_t)i);
+        else tex_bilinear_f(PTO_TAP_PROBE, (const float*)texels, w, h, u[i], v[i], out + 4 * (size_t)i);
+    }
+    return 0;
 }
 
 /* ---------------------------------------------------------------- scene setup */
@@ -559,7 +597,7 @@ static v3 perturbNormal(const pto_frame* f, v3 nl, float nsx, float nsy, float u
     v3 NfromST = v_cross(S, T);
     if (v_dot(NfromST, N) < 0.0f) { S = v_muls(S, -1.0f); T = v_muls(T, -1.0f); }
     float tx[4];
-    tex_bilinear(f->bump, f->bumpW, f->bumpH, u, v, tx);
+    tex_bilinear(PTO_TAP_BUMP, f->bump, f->bumpW, f->bumpH, u, v, tx);
     c->rgba8_taps += 4;
     v3 mapN = V3(tx[0] * 2.0f - 1.0f, tx[1] * 2.0f - 1.0f, tx[2] * 2.0f - 1.0f);
     mapN = v_normalize(mapN);
@@ -760,7 +798,7 @@ static v3 Get_HDR_Color(Inv* s, v3 rayDirection)
     float u = g_atan2(rayDirection.x, rayDirection.z) * 0.15915494309f + 0.5f;
     float v = g_acos(-rayDirection.y) * 0.31830988618379067f;
     float tx[4];
-    tex_bilinear_f(f->hdr, f->hdrW, f->hdrH, u, v, tx);
+    tex_bilinear_f(PTO_TAP_HDR, f->hdr, f->hdrW, f->hdrH, u, v, tx);
     s->c.hdr_taps += 4;
     return v_muls(V3(tx[0], tx[1], tx[2]), f->uHDRExposure);
 }
@@ -788,6 +826,7 @@ static v3 CalculateRadiance(Inv* s, GOut* g)
     g->objectNormal = V3(0, 0, 0); g->objectColor = V3(0, 0, 0); g->objectID = 0.0f; g->pixelSharpness = 0.0f;
 
     for (int bounces = 0; bounces < 6; bounces++) {
+        if (g_tap_rows) g_tap_bounce = bounces;
         previousIntersecType = hitType;
         SceneIntersect(s, s->rayOrigin, s->rayDirection, &h);
         hitType = h.type;
@@ -822,9 +861,9 @@ static v3 CalculateRadiance(Inv* s, GOut* g)
 
         if (gltf && hitType == PBR_MATERIAL) {
             float tx[4];
-            tex_bilinear(f->albedo, f->albedoW, f->albedoH, h.u, h.v, tx); s->c.rgba8_taps += 4;
+            tex_bilinear(PTO_TAP_ALBEDO, f->albedo, f->albedoW, f->albedoH, h.u, h.v, tx); s->c.rgba8_taps += 4;
             h.color = v_pow22(V3(tx[0], tx[1], tx[2]));
-            if (f->uModelUsesEmissiveTexture) { tex_bilinear(f->emissive, f->emissiveW, f->emissiveH, h.u, h.v, tx); s->c.rgba8_taps += 4; emission = V3(tx[0], tx[1], tx[2]); }
+            if (f->uModelUsesEmissiveTexture) { tex_bilinear(PTO_TAP_EMISSIVE, f->emissive, f->emissiveW, f->emissiveH, h.u, h.v, tx); s->c.rgba8_taps += 4; emission = V3(tx[0], tx[1], tx[2]); }
             else emission = V3(0, 0, 0);
             emission = v_pow22(emission);
             float maxEmission = g_max(emission.x, g_max(emission.y, emission.z));
@@ -834,7 +873,7 @@ static v3 CalculateRadiance(Inv* s, GOut* g)
                 break;
             }
             hitType = DIFFUSE;
-            if (f->uModelUsesMetallicTexture) { tex_bilinear(f->metallic, f->metallicW, f->metallicH, h.u, h.v, tx); s->c.rgba8_taps += 4; metallicRoughness = V3(tx[0], tx[1], tx[2]); }
+            if (f->uModelUsesMetallicTexture) { tex_bilinear(PTO_TAP_METALLIC, f->metallic, f->metallicW, f->metallicH, h.u, h.v, tx); s->c.rgba8_taps += 4; metallicRoughness = V3(tx[0], tx[1], tx[2]); }
             else metallicRoughness = V3(0, 0, 0);
             metallicRoughness = v_pow22(metallicRoughness);
             if (metallicRoughness.y > 0.01f) hitType = CLEARCOAT_DIFFUSE;
@@ -1021,6 +1060,7 @@ static v3 CalculateRadianceSky(Inv* s, GOut* g)
     g->objectNormal = V3(0, 0, 0); g->objectColor = V3(0, 0, 0); g->objectID = 0.0f; g->pixelSharpness = 0.0f;
 
     for (int bounces = 0; bounces < 6; bounces++) {
+        if (g_tap_rows) g_tap_bounce = bounces;
         previousIntersecType = hitType;
         SceneIntersect(s, s->rayOrigin, s->rayDirection, &h);
         hitType = h.type;
@@ -1232,6 +1272,8 @@ static int shade_rows(const pto_frame* f, int row0, int row1, int nthreads, Shad
     pto_counters total;
     memset(&total, 0, sizeof(total));
 #ifdef _OPENMP
+    /* (a thread count asked for holds for this call alone: a one-thread tap-log render does not slow the next) */
+    const int threads_before = omp_get_max_threads();
     if (nthreads > 0) omp_set_num_threads(nthreads);
 #pragma omp parallel
 #endif
@@ -1254,6 +1296,9 @@ static int shade_rows(const pto_frame* f, int row0, int row1, int nthreads, Shad
             total.hdr_taps += local.hdr_taps;
         }
     }
+#ifdef _OPENMP
+    if (nthreads > 0) omp_set_num_threads(threads_before);
+#endif
     if (counters) *counters = total;
     *shp = sh; *qy0p = qy0; *qy1p = qy1;
     return Wq;
@@ -1262,6 +1307,7 @@ static int shade_rows(const pto_frame* f, int row0, int row1, int nthreads, Shad
 int pto_path_trace(const pto_frame* f, const float* prev, float* out, int row0, int row1, int nthreads, pto_counters* counters)
 {
     if (!f || !prev || !out || row0 < 0 || row1 > f->height || row0 >= row1 || !f->blueNoise) return -1;
+    if (g_tap_rows && nthreads != 1) return -4;   /* the tap log has one writer */
     if ((f->scene == PTO_SCENE_GLTF || f->scene == PTO_SCENE_HDRI || f->scene == PTO_SCENE_SKYMESH) && (!f->aabb || !f->tri)) return -2;
     Shade* sh; int qy0, qy1;
     int Wq = shade_rows(f, row0, row1, nthreads, &sh, &qy0, &qy1, counters);
@@ -1279,6 +1325,7 @@ int pto_path_trace(const pto_frame* f, const float* prev, float* out, int row0, 
 int pto_gbuffer(const pto_frame* f, float* gbuf, int row0, int row1, int nthreads)
 {
     if (!f || !gbuf || row0 < 0 || row1 > f->height || row0 >= row1) return -1;
+    if (g_tap_rows && nthreads != 1) return -4;
     Shade* sh; int qy0, qy1;
     int Wq = shade_rows(f, row0, row1, nthreads, &sh, &qy0, &qy1, NULL);
     if (Wq < 0) return -3;

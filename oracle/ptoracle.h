@@ -97,6 +97,27 @@ int pto_screen_output_f32(int width, int height, const float* acc, float uOneOve
  * 4 atan, 5 atan2(x, y2), 6 acos, 7 pow(x, y2), 8 exp, 9 log, 10 sqrt, 11 rng stream. */
 int pto_math_probe(int op, const float* x, const float* y2, float* out, int n);
 
+/* The two bilinear samplers of the fragment programs (texture() at LOD 0, LINEAR, REPEAT) on caller-given
+ * texels, once per (u[i], v[i]): kind 0 = RGBA8 (w*h*4 bytes), kind 1 = RGBA32F (w*h*4 floats); out[4n]. */
+int pto_tex_probe(int kind, const void* texels, int w, int h, const float* u, const float* v, float* out, int n);
+
+/* The tap log. While a buffer is bound, every bilinear lookup (pto_path_trace, pto_gbuffer, pto_tex_probe)
+ * appends one row: which map, at which bounce of CalculateRadiance's loop, the coordinates it was given and
+ * the four texel indices it read. Rows beyond
+ * `capacity` are counted, not written. One writer: with a log bound pto_path_trace and pto_gbuffer take
+ * nthreads == 1 only (-4 otherwise). A sampler whose map is unbound reads nothing and logs nothing. */
+enum { PTO_TAP_ALBEDO = 0, PTO_TAP_BUMP = 1, PTO_TAP_METALLIC = 2, PTO_TAP_EMISSIVE = 3, PTO_TAP_HDR = 4,
+       PTO_TAP_PROBE = 5 };
+typedef struct pto_tap {
+    int32_t map;             /* PTO_TAP_* */
+    int32_t bounce;          /* the segment's index in CalculateRadiance's loop, 0 = the primary ray; -1 from the probe */
+    float u, v;
+    int32_t x0, y0, x1, y1;  /* texels (x0,y0) (x1,y0) (x0,y1) (x1,y1) */
+} pto_tap;
+/* Bind rows[capacity] and zero the counts; (NULL, 0) unbinds. */
+int pto_tap_log_bind(pto_tap* rows, int64_t capacity);
+void pto_tap_log_count(int64_t* written, int64_t* dropped);
+
 #ifdef __cplusplus
 }
 #endif

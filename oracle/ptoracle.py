@@ -79,6 +79,10 @@ def lib(variant=""):
         L.pto_math_probe.argtypes = [c_i, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i]
         L.pto_sky_color.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i]
         L.pto_quadric_probe.argtypes = [c_i, c_f, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i]
+        L.pto_tex_probe.argtypes = [c_i, ctypes.c_void_p, c_i, c_i, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i]
+        L.pto_tap_log_bind.argtypes = [ctypes.c_void_p, ctypes.c_int64]
+        L.pto_tap_log_count.argtypes = [P(ctypes.c_int64), P(ctypes.c_int64)]
+        L.pto_tap_log_count.restype = None
         _libs[variant] = L
     return _libs[variant]
 
@@ -181,6 +185,52 @@ def math_probe(op, x, y=None):
     if rc != 0:
         raise RuntimeError("bad op")
     return out
+
+
+def tex_probe(texels, u, v):
+    """The oracle's bilinear sampler on a map given as an array: (h, w, 4) uint8 runs tex_bilinear (RGBA8),
+    (h, w, 4) float32 runs tex_bilinear_f (RGBA32F); one (r, g, b, a) row per (u, v)."""
+    texels = np.asarray(texels)
+    if texels.dtype not in (np.uint8, np.float32) or texels.ndim != 3 or texels.shape[2] != 4:
+        raise ValueError("texels: (h, w, 4) uint8 or float32")
+    texels = np.ascontiguousarray(texels)
+    u = np.ascontiguousarray(u, dtype=np.float32).reshape(-1)
+    v = np.ascontiguousarray(v, dtype=np.float32).reshape(-1)
+    if u.size != v.size:
+        raise ValueError("u and v differ in length")
+    out = np.zeros((u.size, 4), np.float32)
+    rc = lib().pto_tex_probe(0 if texels.dtype == np.uint8 else 1, texels.ctypes.data, texels.shape[1], texels.shape[0],
+                             u.ctypes.data, v.ctypes.data, out.ctypes.data, u.size)
+    if rc != 0:
+        raise RuntimeError("pto_tex_probe failed: %d" % rc)
+    return out
+
+
+TAP_MAPS = ("albedo", "bump", "metallic", "emissive", "hdr", "probe")
+TAP_DTYPE = np.dtype([("map", np.int32), ("bounce", np.int32), ("u", np.float32), ("v", np.float32),
+                      ("x0", np.int32), ("y0", np.int32), ("x1", np.int32), ("y1", np.int32)])
+
+
+class TapLog:
+    """The oracle's tap log over a buffer of `capacity` rows, as a context manager: while it is open, every
+    bilinear lookup of the pinned library appends a row (TAP_DTYPE; `map` indexes TAP_MAPS), and renders must
+    ask for nthreads=1. Afterwards `rows` holds what was written and `dropped` counts what did not fit."""
+
+    def __init__(self, capacity):
+        self._buf = np.zeros(capacity, TAP_DTYPE)
+        self.rows, self.dropped = self._buf[:0], 0
+
+    def __enter__(self):
+        if lib().pto_tap_log_bind(self._buf.ctypes.data, self._buf.size) != 0:
+            raise RuntimeError("pto_tap_log_bind failed")
+        return self
+
+    def __exit__(self, *exc):
+        w, d = ctypes.c_int64(0), ctypes.c_int64(0)
+        lib().pto_tap_log_count(ctypes.byref(w), ctypes.byref(d))
+        lib().pto_tap_log_bind(None, 0)
+        self.rows, self.dropped = self._buf[:w.value], d.value
+        return False
 
 
 def sky_color(sun, dirs):
