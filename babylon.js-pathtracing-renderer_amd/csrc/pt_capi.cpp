@@ -65,6 +65,7 @@ hipError_t pt_launch_denoise(const pt::DenoiseArgs* a, hipStream_t s);
 hipError_t pt_launch_denoise_var(const pt::DenoiseVarArgs* a, hipStream_t s);
 hipError_t pt_launch_jpeg_measure(const ptj::EncArgs* a, hipStream_t s);
 hipError_t pt_launch_jpeg_pack(const ptj::EncArgs* a, hipStream_t s);
+hipError_t pt_launch_jpeg_ship(const ptj::ShipArgs* a, hipStream_t s);
 hipError_t pt_launch_math_probe(int op, const float* x, const float* y, float* out, int n, hipStream_t s);
 hipError_t pt_launch_persist(int prog, int count, const pt::TraceArgs* a, const pt::WfBufs* w, int tiles_x,
                              unsigned n_wave_tiles, unsigned per_wave, unsigned refill, hipStream_t s);
@@ -120,8 +121,29 @@ struct DevFx {
                             // luminance moments (dev_set_moment_target)
 };
 
+// An encode or read job (pt_canvas_encode_jpeg_begin, pt_canvas_read_begin): one of the context's pt::kJobsMax
+// slots, so a handle stays readable for as long as its context lives and a finished one is told by `pending`. The
+// slot keeps its buffers and its event from job to job: `dslot` the device buffer pt_jpeg_pack assembles the stream
+// in (pt::JobLayout::slot_bytes of the canvas, so it fits whatever the pixels), `pinned` the host buffer
+// (pt::JobLayout) that pt_jpeg_ship or the read job's copy fills, `ev` recorded behind them.
+struct pt_job {
+    Dev* dev = nullptr;
+    int slot = 0;
+    bool pending = false;
+    bool jpeg = false;            // else a read job: the canvas's texels in the stream's place
+    int w = 0, h = 0, hs = 1, vs = 1, optimize = 0;
+    ptj::QuantTables qt;
+    size_t room = 0;              // bytes of the stream (or of the texels) the pinned buffer takes for this job
+    size_t stream_max = 0;        // the canvas's bound under this job's tables
+    DevMem dslot;                 // (size in bytes)
+    void* pinned = nullptr;
+    size_t pinned_bytes = 0;
+    hipEvent_t ev = nullptr;
+};
+
 struct Dev {
     int device = 0;
+    void* owner = nullptr;             // the pt_ctx this part belongs to (pt_group.cpp; for a job's error message)
     hipStream_t stream = nullptr;      // the stream all work is enqueued on
     hipStream_t own_stream = nullptr;  // the context's own stream (dev_set_stream(NULL) restores it)
     std::string err;
@@ -153,7 +175,8 @@ struct Dev {
     // buffer set; pt::ContLayout), GB the persistent backend's G-buffer + radiance (pixels), DENOISE pt_denoise's
     // three planes, colour[2] + guide (pixels), DENOISE_VAR pt_denoise_variance's, those and var[2] (pixels), JPEG
     // pt_canvas_encode_jpeg's workspace (bytes; pt::JpegLayout), JPEG_OUT the stream it assembles (bytes) and
-    // JPEG_OPT what optimised Huffman tables add (bytes; pt::JpegOptLayout)
+    // JPEG_OPT what optimised Huffman tables add (bytes; pt::JpegOptLayout). (An encode job's stream buffer is its
+    // slot's own: pt_job::dslot.)
     enum Slab { WF, LPT, SPILL, RAD, FEAT, CONT, GB, DENOISE, DENOISE_VAR, JPEG, JPEG_OUT, JPEG_OPT, kSlabs };
     DevMem slab[kSlabs];
     pt::WfBufs wf = {};
@@ -215,6 +238,11 @@ struct Dev {
     int pending = -1;
     std::set<DevTex*> textures;
     std::set<DevFx*> effects;
+    // encode and read jobs: the slots, their bookkeeping (pt_plan.h), and the stream of a finish's slow copy, which
+    // must not wait for the frames queued behind the job on the main stream
+    pt::Jobs jobs;
+    pt_job job[pt::kJobsMax];
+    hipStream_t job_stream = nullptr;
 };
 
 namespace {
@@ -1174,6 +1202,7 @@ Dev* dev_ctx_create(int device, int* err)
     }
     auto* c = new Dev();
     c->device = device;
+    for (int i = 0; i < pt::kJobsMax; i++) { c->job[i].dev = c; c->job[i].slot = i; }
     c->cu_count = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     pt::read_knobs(c->k);
     c->ov.depth_run = c->k.depth;
@@ -1213,6 +1242,12 @@ void dev_ctx_destroy(Dev* c)
         if (c->ev0[i]) hipEventDestroy(c->ev0[i]);
         if (c->ev1[i]) hipEventDestroy(c->ev1[i]);
     }
+    for (pt_job& j : c->job) {   // (a pending job's work ended with the stream's)
+        j.dslot.release();
+        if (j.pinned) hipHostFree(j.pinned);
+        if (j.ev) hipEventDestroy(j.ev);
+    }
+    if (c->job_stream) hipStreamDestroy(c->job_stream);
     if (c->canvas && !c->canvas_external) hipFree(c->canvas);
     for (DevMem& m : c->slab) m.release();
     for (auto& e : c->tune_ev) if (e) hipEventDestroy(e);
@@ -1793,16 +1828,11 @@ int dev_denoise_variance(Dev* c, const DevTex* beauty, const DevTex* normal_id, 
     return PT_OK;
 }
 
-// pt_canvas_encode_jpeg: an observer of the canvas like dev_read_pixels. The length pass runs first (colour
-// conversion .. the scan of the row lengths); the host reads the stream's length, sizes the stream buffer from it,
-// and the last kernel assembles the stream, which is copied behind the header the host writes. No timing events,
-// no counters; the canvas is only read. With `optimize` the length pass also counts the symbols and builds the
-// Huffman tables (the histograms are zeroed on the stream first), the tables come back with the stream's length in
-// the one copy, and the header, whose length they decide, is written from them.
-int dev_canvas_encode_jpeg(Dev* c, int quality, int subsampling, int optimize, uint8_t* dst, size_t capacity, size_t* size)
+namespace {
+
+// what pt_canvas_encode_jpeg_opt and pt_canvas_encode_jpeg_begin refuse alike
+int jpeg_check(Dev* c, int quality, int subsampling, int optimize)
 {
-    if (!c) return PT_ERR_ARG;
-    if (!dst || !size) return fail(c, PT_ERR_ARG, "pt_canvas_encode_jpeg: dst and size must not be NULL");
     if (quality < 1 || quality > 100) return fail(c, PT_ERR_ARG, "pt_canvas_encode_jpeg: quality must be 1..100");
     if (subsampling < PT_JPEG_444 || subsampling > PT_JPEG_420)
         return fail(c, PT_ERR_ARG, "pt_canvas_encode_jpeg_sub: subsampling must be 0 (4:4:4), 1 (4:2:2) or 2 (4:2:0)");
@@ -1810,10 +1840,14 @@ int dev_canvas_encode_jpeg(Dev* c, int quality, int subsampling, int optimize, u
     if (!c->canvas || c->cw <= 0 || c->ch <= 0) return fail(c, PT_ERR_ARG, "pt_canvas_encode_jpeg: no canvas yet");
     if (c->cw > 65535 || c->ch > 65535)   // (SOF0's 16-bit fields; the DRI field alone would allow 65535 x 8 columns)
         return fail(c, PT_ERR_ARG, "pt_canvas_encode_jpeg: a JPEG is at most 65535 x 65535");
-    HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = flush_deferred(c)) return rc;
-    const int hs = ptj::sampling_h(subsampling), vs = ptj::sampling_v(subsampling);
-    const pt::JpegLayout L(c->cw, c->ch, hs, vs, optimize ? pt::kJpegOptBlockBytes : pt::kJpegBlockBytes);
+    return PT_OK;
+}
+
+// The length pass of the canvas as it stands on the main stream (colour conversion .. the scan of the row lengths,
+// pt_launch_jpeg_measure) in the shared workspace slabs, which grow first where they must; `a` is left ready for
+// pt_launch_jpeg_pack but for a.out. With `optimize` the histograms are zeroed on the stream first.
+int jpeg_measure(Dev* c, int quality, int hs, int vs, int optimize, const pt::JpegLayout& L, ptj::EncArgs& a)
+{
     DevMem& mem = c->slab[Dev::JPEG];
     if (L.bytes > mem.size)
         if (int rc = mem.grow(c, L.bytes, L.bytes, WAIT_MAIN, false)) return rc;
@@ -1821,7 +1855,6 @@ int dev_canvas_encode_jpeg(Dev* c, int quality, int subsampling, int optimize, u
     DevMem& opt = c->slab[Dev::JPEG_OPT];
     if (optimize && O.bytes > opt.size)
         if (int rc = opt.grow(c, O.bytes, O.bytes, WAIT_MAIN, false)) return rc;
-    ptj::EncArgs a;
     std::memset(&a, 0, sizeof(a));
     a.canvas = (const uint32_t*)c->canvas;
     a.width = c->cw; a.height = c->ch;
@@ -1835,11 +1868,6 @@ int dev_canvas_encode_jpeg(Dev* c, int quality, int subsampling, int optimize, u
     a.rowbits = (uint32_t*)(base + L.rowbits); a.rowlen = (uint32_t*)(base + L.rowlen);
     a.rowoff = (unsigned long long*)(base + L.rowoff); a.total = (unsigned long long*)(base + L.total);
     a.qt = ptj::quant_tables(quality);
-    struct {
-        unsigned long long stream;
-        ptj::OptTables tables;
-    } got = {};   // (JpegOptLayout: the tables right behind the length)
-    static_assert(sizeof(got) == 8 + pt::JpegOptLayout::kTables && sizeof(ptj::HuffCodes) == pt::JpegOptLayout::kCodes, "");
     if (optimize) {
         char* ob = opt.as<char>();
         a.hist = (unsigned long long*)(ob + O.hist); a.codes = (ptj::HuffCodes*)(ob + O.codes);
@@ -1847,6 +1875,37 @@ int dev_canvas_encode_jpeg(Dev* c, int quality, int subsampling, int optimize, u
         HIPCHK(c, hipMemsetAsync(a.hist, 0, pt::JpegOptLayout::kHist, c->stream));
     }
     HIPCHK(c, pt_launch_jpeg_measure(&a, c->stream));
+    return PT_OK;
+}
+
+// what the host reads back of a length pass (JpegOptLayout, JobLayout: the tables right behind the length)
+struct JpegResult {
+    unsigned long long stream;
+    ptj::OptTables tables;
+};
+static_assert(sizeof(JpegResult) == 8 + pt::JpegOptLayout::kTables && sizeof(JpegResult) == pt::JobLayout::kResult &&
+              sizeof(ptj::HuffCodes) == pt::JpegOptLayout::kCodes, "");
+
+}  // namespace
+
+// pt_canvas_encode_jpeg: an observer of the canvas like dev_read_pixels. The length pass runs first (colour
+// conversion .. the scan of the row lengths); the host reads the stream's length, sizes the stream buffer from it,
+// and the last kernel assembles the stream, which is copied behind the header the host writes. No timing events,
+// no counters; the canvas is only read. With `optimize` the length pass also counts the symbols and builds the
+// Huffman tables (the histograms are zeroed on the stream first), the tables come back with the stream's length in
+// the one copy, and the header, whose length they decide, is written from them.
+int dev_canvas_encode_jpeg(Dev* c, int quality, int subsampling, int optimize, uint8_t* dst, size_t capacity, size_t* size)
+{
+    if (!c) return PT_ERR_ARG;
+    if (!dst || !size) return fail(c, PT_ERR_ARG, "pt_canvas_encode_jpeg: dst and size must not be NULL");
+    if (int rc = jpeg_check(c, quality, subsampling, optimize)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = flush_deferred(c)) return rc;
+    const int hs = ptj::sampling_h(subsampling), vs = ptj::sampling_v(subsampling);
+    const pt::JpegLayout L(c->cw, c->ch, hs, vs, optimize ? pt::kJpegOptBlockBytes : pt::kJpegBlockBytes);
+    ptj::EncArgs a;
+    if (int rc = jpeg_measure(c, quality, hs, vs, optimize, L, a)) return rc;
+    JpegResult got = {};
     HIPCHK(c, hipMemcpyAsync(&got, a.total, optimize ? sizeof(got) : sizeof(got.stream), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const unsigned long long stream = got.stream;
@@ -1872,6 +1931,187 @@ int dev_canvas_encode_jpeg(Dev* c, int quality, int subsampling, int optimize, u
     if (optimize) std::memcpy(dst, head, header);
     else ptj::write_header(dst, c->cw, c->ch, a.qt, hs, vs);   // (while the stream is on its way)
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
+// ---- encode and read jobs: the two observers of the canvas without a host wait (include/pt.h) ----
+// begin enqueues on the main stream, in stream order behind the output pass that wrote the canvas and before the
+// next one: the length pass, pt_jpeg_pack into the slot's own device buffer, pt_jpeg_ship into the slot's pinned
+// buffer (a read job: one copy of the texels into it), and the slot's event. It does not run what pt::MainPlan
+// defers: the canvas is written by an output pass only, and that pass is enqueued when its draw call returns (an
+// empty pass writes nothing), so the canvas is never pending. It waits only where a buffer must be made or grow.
+namespace {
+
+// the slot of the next job, with a pinned buffer of a stream (or texels) of `room` bytes at least, and its event
+int job_take(Dev* c, size_t room, pt_job** out)
+{
+    const int s = c->jobs.free_slot();
+    if (s < 0) return fail(c, PT_ERR_STATE, "pt_job: PT_JOBS_MAX jobs are pending; finish or cancel one first");
+    pt_job& j = c->job[s];
+    const pt::JobLayout H(room);
+    if (H.bytes > j.pinned_bytes) {   // (the slot is free: nothing runs on its buffers)
+        if (j.pinned) HIPCHK(c, hipHostFree(j.pinned));
+        j.pinned = nullptr; j.pinned_bytes = 0;
+        HIPCHK(c, hipHostMalloc(&j.pinned, H.bytes, hipHostMallocDefault));
+        j.pinned_bytes = H.bytes;
+    }
+    if (!j.ev) HIPCHK(c, hipEventCreateWithFlags(&j.ev, hipEventDefault));
+    j.room = room;
+    *out = &j;
+    return PT_OK;
+}
+
+// the job is enqueued: its event (default flags: the release behind pt_jpeg_ship's stores reaches the host)
+int job_begun(Dev* c, pt_job* j)
+{
+    HIPCHK(c, hipEventRecord(j->ev, c->stream));
+    c->jobs.take(j->slot);
+    j->pending = true;
+    return PT_OK;
+}
+
+}  // namespace
+
+int dev_job_begin_jpeg(Dev* c, int quality, int subsampling, int optimize, pt_job** job)
+{
+    if (job) *job = nullptr;
+    if (!c) return PT_ERR_ARG;
+    if (!job) return fail(c, PT_ERR_ARG, "pt_canvas_encode_jpeg_begin: job must not be NULL");
+    if (int rc = jpeg_check(c, quality, subsampling, optimize)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const int hs = ptj::sampling_h(subsampling), vs = ptj::sampling_v(subsampling);
+    const pt::JpegLayout L(c->cw, c->ch, hs, vs, optimize ? pt::kJpegOptBlockBytes : pt::kJpegBlockBytes);
+    pt_job* j = nullptr;
+    if (int rc = job_take(c, c->jobs.room(L.stream_max()), &j)) return rc;
+    const size_t need = pt::JobLayout::slot_bytes(c->cw, c->ch, hs, vs);
+    if (need > j->dslot.size) {   // (the slot is free; hipFree waits for the device)
+        j->dslot.release();
+        HIPCHK(c, j->dslot.alloc(need));
+        j->dslot.size = need;
+    }
+    ptj::EncArgs a;
+    if (int rc = jpeg_measure(c, quality, hs, vs, optimize, L, a)) return rc;
+    a.out = j->dslot.as<uint8_t>();
+    HIPCHK(c, pt_launch_jpeg_pack(&a, c->stream));
+    const pt::JobLayout H(j->room);
+    char* host = (char*)j->pinned;
+    ptj::ShipArgs sa;
+    sa.stream = a.out; sa.total = a.total; sa.tables = optimize ? a.tables : nullptr;
+    sa.room = j->room;
+    sa.host_stream = (uint8_t*)(host + H.stream);
+    sa.host_total = (unsigned long long*)(host + H.result);
+    sa.host_tables = (ptj::OptTables*)(host + H.result + 8);
+    HIPCHK(c, pt_launch_jpeg_ship(&sa, c->stream));
+    j->jpeg = true;
+    j->w = c->cw; j->h = c->ch; j->hs = hs; j->vs = vs; j->optimize = optimize;
+    j->qt = a.qt;
+    j->stream_max = L.stream_max();
+    if (int rc = job_begun(c, j)) return rc;
+    *job = j;
+    return PT_OK;
+}
+
+int dev_job_begin_read(Dev* c, pt_job** job)
+{
+    if (job) *job = nullptr;
+    if (!c) return PT_ERR_ARG;
+    if (!job) return fail(c, PT_ERR_ARG, "pt_canvas_read_begin: job must not be NULL");
+    if (!c->canvas || c->cw <= 0 || c->ch <= 0) return fail(c, PT_ERR_ARG, "pt_canvas_read_begin: no canvas yet");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t bytes = (size_t)c->cw * c->ch * sizeof(uchar4);
+    pt_job* j = nullptr;
+    if (int rc = job_take(c, bytes, &j)) return rc;
+    HIPCHK(c, hipMemcpyAsync((char*)j->pinned + pt::JobLayout(bytes).stream, c->canvas, bytes, hipMemcpyDeviceToHost, c->stream));
+    j->jpeg = false;
+    j->w = c->cw; j->h = c->ch;
+    if (int rc = job_begun(c, j)) return rc;
+    *job = j;
+    return PT_OK;
+}
+
+Dev* dev_job_dev(pt_job* j) { return j ? j->dev : nullptr; }
+void dev_set_owner(Dev* c, void* owner) { c->owner = owner; }
+void* dev_owner(Dev* c) { return c->owner; }
+
+int dev_job_poll(pt_job* j, int* done)
+{
+    if (!j || !j->dev) return PT_ERR_ARG;
+    Dev* c = j->dev;
+    if (!j->pending || !done) return fail(c, PT_ERR_ARG, "pt_job_poll: no pending job, or done is NULL");
+    const hipError_t e = hipEventQuery(j->ev);
+    if (e != hipSuccess && e != hipErrorNotReady) return hipfail(c, e, "hipEventQuery");
+    *done = e == hipSuccess;
+    return PT_OK;
+}
+
+// Waits for the job's event alone, so the frames queued behind it keep running. The header is written here, from
+// the tables in the result block; the stream beyond the pinned buffer's room, when the file outgrew the prediction,
+// comes from the slot's device buffer by a blocking copy on a stream of its own.
+int dev_job_finish(pt_job* j, uint8_t* dst, size_t capacity, size_t* size)
+{
+    if (!j || !j->dev) return PT_ERR_ARG;
+    Dev* c = j->dev;
+    if (!j->pending) return fail(c, PT_ERR_ARG, "pt_job_finish: the job was finished or cancelled");
+    if (!size || (!dst && capacity)) return fail(c, PT_ERR_ARG, "pt_job_finish: dst and size must not be NULL");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipEventSynchronize(j->ev));
+    const pt::JobLayout H(j->room);
+    const char* host = (const char*)j->pinned;
+    if (!j->jpeg) {
+        *size = j->room;
+        if (capacity < *size) return fail(c, PT_ERR_ARG, "pt_job_finish: destination too small");
+        std::memcpy(dst, host + H.stream, *size);
+        j->pending = false;
+        c->jobs.release(j->slot, false);
+        return PT_OK;
+    }
+    const JpegResult* got = (const JpegResult*)(host + H.result);
+    const size_t stream = (size_t)got->stream;
+    if (got->stream > j->stream_max) return fail(c, PT_ERR_STATE, "pt_job_finish: the stream's length is past its bound");
+    uint8_t head[ptj::kOptHeaderMax];
+    size_t header;
+    if (j->optimize) {
+        for (int t = 0; t < 4; t++)
+            if (ptj::opt_table_symbols(got->tables, t) < 1)
+                return fail(c, PT_ERR_STATE, "pt_job_finish: the device built no Huffman table");
+        header = ptj::write_header(head, j->w, j->h, j->qt, j->hs, j->vs, got->tables);
+    } else {
+        header = ptj::write_header(head, j->w, j->h, j->qt, j->hs, j->vs);
+    }
+    *size = header + stream;
+    if (capacity < *size) return fail(c, PT_ERR_ARG, "pt_job_finish: destination too small");
+    const size_t fast = stream < j->room ? stream : j->room;
+    if (stream > fast) {   // before dst is written: an error here leaves the job as it was
+        if (!c->job_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->job_stream, hipStreamNonBlocking));
+        HIPCHK(c, hipMemcpyAsync(dst + header + fast, j->dslot.as<uint8_t>() + fast, stream - fast, hipMemcpyDeviceToHost,
+                                 c->job_stream));
+        HIPCHK(c, hipStreamSynchronize(c->job_stream));
+    }
+    std::memcpy(dst, head, header);
+    std::memcpy(dst + header, host + H.stream, fast);
+    c->jobs.shipped(stream, j->room);
+    j->pending = false;
+    c->jobs.release(j->slot, false);
+    return PT_OK;
+}
+
+// waits for the job's device work, so that the slot's buffers are never reused under a running kernel
+int dev_job_cancel(pt_job* j)
+{
+    if (!j || !j->dev) return PT_ERR_ARG;
+    Dev* c = j->dev;
+    if (!j->pending) return fail(c, PT_ERR_ARG, "pt_job_cancel: the job was finished or cancelled");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipEventSynchronize(j->ev));
+    j->pending = false;
+    c->jobs.release(j->slot, true);
+    return PT_OK;
+}
+
+int dev_job_stats(Dev* c, uint64_t out[4])
+{
+    if (!c || !out) return PT_ERR_ARG;
+    out[0] = c->jobs.begun; out[1] = c->jobs.finished; out[2] = c->jobs.slow; out[3] = c->jobs.cancelled;
     return PT_OK;
 }
 

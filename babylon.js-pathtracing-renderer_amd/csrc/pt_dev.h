@@ -74,6 +74,16 @@ int dev_denoise_variance(Dev* c, const DevTex* beauty, const DevTex* normal_id, 
                          const DevTex* moments, DevTex* dst, int iterations, float sigma_normal, float sigma_luminance,
                          int demodulate);
 int dev_canvas_encode_jpeg(Dev* c, int quality, int subsampling, int optimize, uint8_t* dst, size_t capacity, size_t* size);
+// encode and read jobs (one-part contexts): a pt_job is a slot of its part, valid for the part's lifetime
+int dev_job_begin_jpeg(Dev* c, int quality, int subsampling, int optimize, pt_job** job);
+int dev_job_begin_read(Dev* c, pt_job** job);
+int dev_job_poll(pt_job* job, int* done);
+int dev_job_finish(pt_job* job, uint8_t* dst, size_t capacity, size_t* size);
+int dev_job_cancel(pt_job* job);
+int dev_job_stats(Dev* c, uint64_t out[4]);
+Dev* dev_job_dev(pt_job* job);
+void dev_set_owner(Dev* c, void* owner);   // the context a part belongs to, for the calls that get a job alone
+void* dev_owner(Dev* c);
 int dev_math_exhaustive(Dev* c, int op, uint64_t* mismatches);
 int dev_math_probe(Dev* c, int op, const float* x, const float* y, float* out, int n);
 

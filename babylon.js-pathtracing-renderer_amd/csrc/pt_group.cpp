@@ -257,6 +257,7 @@ pt_ctx* pt_ctx_create_devices(const int* devices, int n, int* err)
         Dev* d = dev_ctx_create(devices[k], &rc);
         if (!d) break;
         c->parts.push_back(d);
+        dev_set_owner(d, c);
         if (n > 1) {
             rc = dev_set_row_partition(d, n, k);
             if (rc == PT_OK) rc = dev_set_output_partition(d, 1);
@@ -556,6 +557,46 @@ int pt_canvas_encode_jpeg_sub(pt_ctx* c, int quality, int subsampling, uint8_t* 
 int pt_canvas_encode_jpeg(pt_ctx* c, int quality, uint8_t* dst, size_t capacity, size_t* size)
 {
     return pt_canvas_encode_jpeg_sub(c, quality, PT_JPEG_444, dst, capacity, size);
+}
+
+// Encode and read jobs: one-part contexts only (a gathered canvas is ordered by events of this layer, and the
+// synchronous calls serve it). A job belongs to its part; the calls that get a job alone find the context through it.
+int pt_canvas_encode_jpeg_begin(pt_ctx* c, int quality, int subsampling, int optimize, pt_job** job)
+{
+    if (job) *job = nullptr;
+    if (!c) return PT_ERR_ARG;
+    if (c->n() > 1) return fail(c, PT_ERR_UNSUPPORTED, "pt_canvas_encode_jpeg_begin needs a one-part context");
+    return take(c, 0, dev_job_begin_jpeg(c->parts[0], quality, subsampling, optimize, job));
+}
+
+int pt_canvas_read_begin(pt_ctx* c, pt_job** job)
+{
+    if (job) *job = nullptr;
+    if (!c) return PT_ERR_ARG;
+    if (c->n() > 1) return fail(c, PT_ERR_UNSUPPORTED, "pt_canvas_read_begin needs a one-part context");
+    return take(c, 0, dev_job_begin_read(c->parts[0], job));
+}
+
+namespace {
+int job_rc(pt_job* job, int rc)
+{
+    Dev* d = dev_job_dev(job);
+    pt_ctx* c = d ? (pt_ctx*)dev_owner(d) : nullptr;
+    return c ? take(c, 0, rc) : rc;
+}
+}  // namespace
+
+int pt_job_poll(pt_job* job, int* done) { return job_rc(job, dev_job_poll(job, done)); }
+int pt_job_finish(pt_job* job, uint8_t* dst, size_t capacity, size_t* size)
+{
+    return job_rc(job, dev_job_finish(job, dst, capacity, size));
+}
+int pt_job_cancel(pt_job* job) { return job_rc(job, dev_job_cancel(job)); }
+
+int pt_job_stats(pt_ctx* c, uint64_t out[4])
+{
+    if (!c || !out) return PT_ERR_ARG;
+    return sum_parts<4>(c, out, dev_job_stats);
 }
 
 int pt_write_pixels(pt_ctx* c, pt_texture* t, const void* src, size_t bytes)

@@ -273,4 +273,17 @@ struct EncArgs {
     OptTables* tables;             // ... and the tables for the header, behind `total`
 };
 
+// pt_jpeg_ship's arguments (an encode job: pt_canvas_encode_jpeg_begin): the stream pt_jpeg_pack assembled in the
+// job's device slot, the length and tables the length pass left, and where they go in the job's pinned host buffer
+// (pt::JobLayout). `room` bytes of the stream at most are copied; both stream buffers are 16-byte aligned.
+struct ShipArgs {
+    const uint8_t* stream;
+    const unsigned long long* total;
+    const OptTables* tables;       // nullptr with the Annex K tables
+    size_t room;
+    uint8_t* host_stream;
+    unsigned long long* host_total;
+    OptTables* host_tables;
+};
+
 }  // namespace ptj

@@ -29,6 +29,9 @@
 //                        the four global histograms.
 //   pt_jpeg_build_tables a wave per table: libjpeg's jpeg_gen_optimal_table, the tables for the header and the codes.
 //   pt_jpeg_block_bits   a wave per MCU: every block's AC bit count again, under those codes.
+// An encode job (pt_canvas_encode_jpeg_begin) runs the same kernels with pt_jpeg_pack writing into the job's own
+// device slot of stream_max() bytes, so that the host need not know the length first, and one more behind them:
+//   pt_jpeg_ship         the stream, its length and the tables into the job's pinned host buffer, 16 bytes a lane.
 // No kernel writes outside the workspace whatever the pixels: a block's bits are bounded by kJpegBlockBytes, or
 // kJpegOptBlockBytes under tables of any code lengths up to 16 (pt_plan.h), because the quantiser clamps to the
 // categories the tables have, and the stream buffer is allocated from the length pt_jpeg_scan_rows computed.
@@ -564,6 +567,28 @@ __global__ __launch_bounds__(256) void pt_jpeg_pack(EncArgs a)
     }
 }
 
+// An encode job's stream from its device slot to the job's pinned host buffer: min(length, room) bytes, a uint4 per
+// lane and consecutive lanes consecutive addresses (a block moves 4 KiB per turn), the last length % 16 bytes one
+// by one; block 0 also leaves the length and, with optimised tables, the tables in the buffer's result block. The
+// host reads the buffer after the event recorded behind this kernel, whose release is system-scope.
+constexpr unsigned kShipBlocks = 256;
+__global__ __launch_bounds__(256) void pt_jpeg_ship(ShipArgs a)
+{
+    const unsigned long long length = *a.total;
+    const size_t n = length < a.room ? (size_t)length : a.room;
+    const uint4* src = (const uint4*)a.stream;
+    uint4* dst = (uint4*)a.host_stream;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n / 16; i += (size_t)gridDim.x * 256) dst[i] = src[i];
+    if (blockIdx.x != 0) return;
+    const size_t tail = (n & ~(size_t)15) + threadIdx.x;
+    if (threadIdx.x < 16 && tail < n) a.host_stream[tail] = a.stream[tail];
+    if (threadIdx.x == 0) *a.host_total = length;
+    // (the tables stand right behind a length on either side, so they are 8-byte aligned and no more)
+    static_assert(sizeof(OptTables) % 8 == 0 && sizeof(OptTables) / 8 <= 256, "the tables in one turn of 8-byte lanes");
+    if (a.tables && threadIdx.x < sizeof(OptTables) / 8)
+        ((unsigned long long*)a.host_tables)[threadIdx.x] = ((const unsigned long long*)a.tables)[threadIdx.x];
+}
+
 }  // namespace ptj
 
 // the three kernels that know the MCU's blocks, at Y's sampling HS x VS
@@ -601,5 +626,14 @@ extern "C" hipError_t pt_launch_jpeg_measure(const ptj::EncArgs* a, hipStream_t 
 extern "C" hipError_t pt_launch_jpeg_pack(const ptj::EncArgs* a, hipStream_t s)
 {
     hipLaunchKernelGGL(ptj::pt_jpeg_pack, dim3(a->tiles < 32u ? a->tiles : 32u, a->rows), dim3(256), 0, s, *a);
+    return hipGetLastError();
+}
+
+// ... and, for an encode job, from the job's device slot to its pinned host buffer with the length and the tables
+extern "C" hipError_t pt_launch_jpeg_ship(const ptj::ShipArgs* a, hipStream_t s)
+{
+    const size_t turns = (a->room + 4095) / 4096;
+    const unsigned blocks = turns < 1 ? 1u : turns < ptj::kShipBlocks ? (unsigned)turns : ptj::kShipBlocks;
+    hipLaunchKernelGGL(ptj::pt_jpeg_ship, dim3(blocks), dim3(256), 0, s, *a);
     return hipGetLastError();
 }

@@ -227,6 +227,64 @@ struct JpegOptLayout {
     }
 };
 
+// Encode and read jobs (pt_canvas_encode_jpeg_begin, pt_canvas_read_begin; pt_capi.cpp): the asynchronous forms of
+// the canvas's observers. A job slot owns a device buffer, JPEG_JOB, that takes the whole stream whatever the pixels
+// (JobLayout::slot_bytes: stream_max() of the canvas under the longer blocks of either choice of tables), so
+// pt_jpeg_pack needs no length from the host, and a pinned host buffer that pt_jpeg_ship fills: result
+// [8 B the stream's length | ptj::OptTables, 1088 B] | stream [`room` bytes]. A read job's texels take the place of
+// the stream. Both stream buffers start on 256 B, so the 16-byte lanes of pt_jpeg_ship are aligned on either side.
+constexpr int kJobsMax = 4;   // PT_JOBS_MAX
+struct JobLayout {
+    static constexpr size_t kResult = 8 + JpegOptLayout::kTables;
+    size_t result, stream, bytes;
+    explicit JobLayout(size_t room)
+    {
+        Carve c;
+        result = c.take(kResult); stream = c.take(room);
+        bytes = c.at;
+    }
+    static size_t slot_bytes(int width, int height, int hs, int vs)
+    {
+        return align256(JpegLayout(width, height, hs, vs, kJpegOptBlockBytes).stream_max());
+    }
+};
+// The slots' bookkeeping: which slot a begin takes (the lowest free one), the refusal when kJobsMax are pending,
+// release on finish or cancel, the four numbers of pt_job_stats, and `room`, the pinned stream capacity the next
+// job is given. It is jpeg_out_room of the longest stream a job has shipped, so it starts at 64 KiB, never shrinks,
+// and grows by a quarter past a file that did not fit (the job that met it was finished through the slow copy).
+struct Jobs {
+    bool busy[kJobsMax] = {};
+    size_t longest = 0;
+    uint64_t begun = 0, finished = 0, slow = 0, cancelled = 0;
+    int pending() const
+    {
+        int n = 0;
+        for (bool b : busy) n += b;
+        return n;
+    }
+    int free_slot() const   // -1: kJobsMax pending
+    {
+        for (int s = 0; s < kJobsMax; s++)
+            if (!busy[s]) return s;
+        return -1;
+    }
+    void take(int slot) { busy[slot] = true; begun++; }
+    size_t room(size_t stream_max) const { return jpeg_out_room(longest, stream_max); }
+    // a job's stream of `length` bytes arrived in a pinned buffer of `had` bytes: true when the rest needs the slow copy
+    bool shipped(size_t length, size_t had)
+    {
+        if (length > longest) longest = length;
+        if (length <= had) return false;
+        slow++;
+        return true;
+    }
+    void release(int slot, bool cancel)
+    {
+        busy[slot] = false;
+        (cancel ? cancelled : finished)++;
+    }
+};
+
 // Frame overlap of the megakernel's draws (pt_capi.cpp, Dev): the sequencing state. Draw k = mk_seq takes buffer
 // set k % (depth + lag) and side stream k % depth, and its path tracing waits for the mark of draw
 // k - depth - lag + 1, or of the oldest draw after everything it must wait for (mark_floor).

@@ -24,6 +24,8 @@
 //   effect.setMomentTarget(momentsRT)             -> pt_set_moment_target (extension: accumulated luminance moments)
 //   engine.denoiseVariance(beautyRT, normalRT, albedoRT, momentsRT, dstRT, opts) -> pt_denoise_variance
 //   engine.encodeCanvasJPEG(quality, subsampling, optimize) -> pt_canvas_encode_jpeg_opt (extension: the canvas as a JPEG file)
+//   engine.encodeCanvasJPEGBegin(q, s, o) / readCanvasBegin() -> pt_canvas_encode_jpeg_begin / pt_canvas_read_begin
+//                                (extension: the same without a host wait; a job with done(), finish(), cancel())
 'use strict';
 const fs = require('fs');
 const path = require('path');
@@ -207,6 +209,23 @@ function install(BABYLON, opts) {
       this._jpegCapacity = Math.max(buf.length, size);
       return buf.subarray(0, size);
     }
+    // MI355X extension (pt_canvas_encode_jpeg_begin): encodeCanvasJPEG without the host wait. Everything is queued
+    // behind the draws so far; the returned job's finish() is the file the synchronous call would have returned
+    // now, whatever is drawn in between. At most 4 jobs are pending; no deferred screenCopy runs.
+    encodeCanvasJPEGBegin(quality = 90, subsampling = 0, optimize = false) {
+      const h = addon.pt_canvas_encode_jpeg_begin(this._pt, quality | 0, subsampling | 0, optimize ? 1 : 0);
+      if (typeof h === 'number') { check(this._pt, h, 'encodeCanvasJPEGBegin'); return null; }
+      return new Job(this, h);
+    }
+    // MI355X extension (pt_canvas_read_begin): readCanvas without the host wait; finish() is the RGBA8 canvas, rows
+    // bottom-up, as of this call
+    readCanvasBegin() {
+      const h = addon.pt_canvas_read_begin(this._pt);
+      if (typeof h === 'number') { check(this._pt, h, 'readCanvasBegin'); return null; }
+      return new Job(this, h);
+    }
+    // [jobs begun, finished, of those through the slow copy, cancelled] since the engine was created
+    jobStats() { return addon.pt_job_stats(this._pt); }
     // MI355X extension (pt_denoise): the edge-avoiding a-trous filter of the RenderTargetTexture `beauty`, guided
     // by the feature targets accumulated beside it (effect.setFeatureTargets), into `dst`: the accumulation's
     // scale, sharpness flags 1, so screenOutput with `dst` as its accumulationBuffer tone-maps it unchanged.
@@ -229,6 +248,31 @@ function install(BABYLON, opts) {
         o.sigmaLuminance === undefined ? 4.0 : +o.sigmaLuminance, o.demodulate === undefined || o.demodulate ? 1 : 0), 'denoiseVariance');
     }
     dispose() { if (this._pt) { addon.pt_ctx_destroy(this._pt); this._pt = null; } super.dispose(); }
+  }
+
+  // A pending encode or read job (engine.encodeCanvasJPEGBegin, readCanvasBegin): done() never blocks, finish()
+  // waits for this job only and returns its bytes as a Buffer, cancel() gives the slot back without them. Dead
+  // after finish() or cancel(), and with its engine.
+  class Job {
+    constructor(engine, handle) { this._engine = engine; this._pt = handle; }
+    done() {
+      const [rc, flag] = addon.pt_job_poll(this._pt);
+      check(this._engine._pt, rc, 'job.done');
+      return flag === 1;
+    }
+    finish() {
+      let buf = Buffer.allocUnsafe(this._engine._jobCapacity || 65536);
+      let [rc, size] = addon.pt_job_finish(this._pt, buf);
+      if (rc !== 0 && size > buf.length) {   // (the job stays valid: once more with the length it reported)
+        buf = Buffer.allocUnsafe(size);
+        [rc, size] = addon.pt_job_finish(this._pt, buf);
+      }
+      check(this._engine._pt, rc, 'job.finish');
+      this._engine._jobCapacity = Math.max(buf.length, size);
+      this._pt = null;
+      return buf.subarray(0, size);
+    }
+    cancel() { check(this._engine._pt, addon.pt_job_cancel(this._pt), 'job.cancel'); this._pt = null; }
   }
 
   class RenderTargetTexture {

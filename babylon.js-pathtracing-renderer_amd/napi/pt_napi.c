@@ -313,6 +313,59 @@ static napi_value CanvasEncodeJpegOpt(napi_env env, napi_callback_info info)
     CHECK(napi_set_element(env, r, 1, num(env, (double)size)));
     return r;
 }
+/* pt_canvas_encode_jpeg_begin(ctx, quality, subsampling, optimize) -> the job (an external), or the status */
+static napi_value CanvasEncodeJpegBegin(napi_env env, napi_callback_info info)
+{
+    napi_value a[MAXARGS]; if (args(env, info, a, 4) < 0) return NULL;
+    pt_job* job = NULL;
+    const int rc = pt_canvas_encode_jpeg_begin((pt_ctx*)handle(env, a[0]), i32(env, a[1]), i32(env, a[2]), i32(env, a[3]), &job);
+    return job ? ext(env, job) : num(env, rc);
+}
+/* pt_canvas_read_begin(ctx) -> the job, or the status */
+static napi_value CanvasReadBegin(napi_env env, napi_callback_info info)
+{
+    napi_value a[MAXARGS]; if (args(env, info, a, 1) < 0) return NULL;
+    pt_job* job = NULL;
+    const int rc = pt_canvas_read_begin((pt_ctx*)handle(env, a[0]), &job);
+    return job ? ext(env, job) : num(env, rc);
+}
+/* pt_job_poll(job) -> [status, done] */
+static napi_value JobPoll(napi_env env, napi_callback_info info)
+{
+    napi_value a[MAXARGS], r; if (args(env, info, a, 1) < 0) return NULL;
+    int done = 0;
+    const int rc = pt_job_poll((pt_job*)handle(env, a[0]), &done);
+    CHECK(napi_create_array_with_length(env, 2, &r));
+    CHECK(napi_set_element(env, r, 0, num(env, rc)));
+    CHECK(napi_set_element(env, r, 1, num(env, done)));
+    return r;
+}
+/* pt_job_finish(job, out: Uint8Array) -> [status, size], as pt_canvas_encode_jpeg: with PT_ERR_ARG and a size past
+ * out's length the job stays valid */
+static napi_value JobFinish(napi_env env, napi_callback_info info)
+{
+    napi_value a[MAXARGS], r; if (args(env, info, a, 2) < 0) return NULL;
+    size_t cap, size = 0; uint8_t* p = (uint8_t*)bytes_of(env, a[1], &cap);
+    if (!p) { napi_throw_type_error(env, NULL, "typed array expected"); return NULL; }
+    const int rc = pt_job_finish((pt_job*)handle(env, a[0]), p, cap, &size);
+    CHECK(napi_create_array_with_length(env, 2, &r));
+    CHECK(napi_set_element(env, r, 0, num(env, rc)));
+    CHECK(napi_set_element(env, r, 1, num(env, (double)size)));
+    return r;
+}
+static napi_value JobCancel(napi_env env, napi_callback_info info)
+{ napi_value a[MAXARGS]; if (args(env, info, a, 1) < 0) return NULL; return num(env, pt_job_cancel((pt_job*)handle(env, a[0]))); }
+/* pt_job_stats(ctx) -> [begun, finished, finished through the slow copy, cancelled], or the status */
+static napi_value JobStats(napi_env env, napi_callback_info info)
+{
+    napi_value a[MAXARGS], r; if (args(env, info, a, 1) < 0) return NULL;
+    uint64_t out[4] = { 0, 0, 0, 0 };
+    const int rc = pt_job_stats((pt_ctx*)handle(env, a[0]), out);
+    if (rc) return num(env, rc);
+    CHECK(napi_create_array_with_length(env, 4, &r));
+    for (uint32_t i = 0; i < 4; i++) CHECK(napi_set_element(env, r, i, num(env, (double)out[i])));
+    return r;
+}
 static napi_value WritePixels(napi_env env, napi_callback_info info)
 {
     napi_value a[MAXARGS]; if (args(env, info, a, 3) < 0) return NULL;
@@ -526,6 +579,9 @@ static napi_value Init(napi_env env, napi_value exports)
         { "pt_render", Render }, { "pt_read_pixels", ReadPixels }, { "pt_write_pixels", WritePixels },
         { "pt_canvas_encode_jpeg", CanvasEncodeJpeg }, { "pt_canvas_encode_jpeg_sub", CanvasEncodeJpegSub },
         { "pt_canvas_encode_jpeg_opt", CanvasEncodeJpegOpt },
+        { "pt_canvas_encode_jpeg_begin", CanvasEncodeJpegBegin }, { "pt_canvas_read_begin", CanvasReadBegin },
+        { "pt_job_poll", JobPoll }, { "pt_job_finish", JobFinish }, { "pt_job_cancel", JobCancel },
+        { "pt_job_stats", JobStats },
         { "pt_set_row_partition", RowPartition }, { "pt_set_backend", SetBackend }, { "pt_set_output_partition", SetOutputPartition }, { "pt_canvas_wrap", CanvasWrap }, { "pt_set_bvh_layout", SetBvhLayout },
         { "pt_bvh_layout_used", BvhLayoutUsed }, { "pt_set_stream", SetStream }, { "pt_texture_device_ptr", TexDevicePtr },
         { "pt_last_render_ms", LastRenderMs }, { "pt_timing_begin", TimingBegin }, { "pt_timing_end", TimingEnd },

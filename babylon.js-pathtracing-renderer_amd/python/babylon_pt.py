@@ -39,6 +39,7 @@ SYMBOLS = [
     "pt_texture_create_rgba32f", "pt_texture_create_rgba8", "pt_render_target_create", "pt_render_target_wrap",
     "pt_render_target_resize", "pt_texture_size", "pt_texture_destroy",
     "pt_render", "pt_read_pixels", "pt_canvas_encode_jpeg", "pt_canvas_encode_jpeg_sub", "pt_canvas_encode_jpeg_opt",
+    "pt_canvas_encode_jpeg_begin", "pt_canvas_read_begin", "pt_job_poll", "pt_job_finish", "pt_job_cancel", "pt_job_stats",
     "pt_write_pixels",
     "pt_set_row_partition", "pt_set_output_partition", "pt_canvas_wrap", "pt_set_backend", "pt_set_bvh_layout", "pt_bvh_layout_used", "pt_set_stream", "pt_texture_device_ptr", "pt_last_render_ms", "pt_timing_begin", "pt_timing_end", "pt_timing_latency",
     "pt_set_counting", "pt_read_counters", "pt_reset_counters", "pt_queue_stats", "pt_cont_stats", "pt_fuse_stats", "pt_set_feature_targets", "pt_denoise", "pt_set_moment_target", "pt_denoise_variance", "pt_math_probe", "pt_math_exhaustive", "pt_bvh_build", "pt_bvh_build_gpu", "pt_jpeg_size", "pt_jpeg_decode_rgba8", "pt_version",
@@ -78,6 +79,11 @@ def lib():
         "pt_canvas_encode_jpeg": ([vp, i32, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)], i32),
         "pt_canvas_encode_jpeg_sub": ([vp, i32, i32, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)], i32),
         "pt_canvas_encode_jpeg_opt": ([vp, i32, i32, i32, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)], i32),
+        "pt_canvas_encode_jpeg_begin": ([vp, i32, i32, i32, ctypes.POINTER(vp)], i32),
+        "pt_canvas_read_begin": ([vp, ctypes.POINTER(vp)], i32),
+        "pt_job_poll": ([vp, ip], i32),
+        "pt_job_finish": ([vp, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)], i32),
+        "pt_job_cancel": ([vp], i32), "pt_job_stats": ([vp, ctypes.POINTER(ctypes.c_uint64)], i32),
         "pt_set_row_partition": ([vp, i32, i32], i32), "pt_texture_device_ptr": ([vp], vp),
         "pt_set_backend": ([vp, i32], i32), "pt_set_output_partition": ([vp, i32], i32),
         "pt_canvas_wrap": ([vp, i32, i32, vp], i32), "pt_set_stream": ([vp, vp], i32),
@@ -102,8 +108,8 @@ def lib():
         "pt_queue_stats": ([vp, ctypes.POINTER(ctypes.c_uint32)], i32), "pt_version": ([], ctypes.c_char_p),
     }
     for name, (args, res) in sig.items():
-        if name == "pt_fuse_stats" and not hasattr(L, name):
-            continue   # (a libpt.so from before the fused pass, loaded through PT_LIBPT for an A/B)
+        if (name == "pt_fuse_stats" or "_begin" in name or name.startswith("pt_job_")) and not hasattr(L, name):
+            continue   # (a libpt.so from before the fused pass or the jobs, loaded through PT_LIBPT for an A/B)
         fn = getattr(L, name)
         fn.argtypes = args
         fn.restype = res
@@ -144,7 +150,9 @@ class Engine:
 
     def check(self, rc, what=""):
         if rc != 0:
-            raise PtError("%s: %s (%s)" % (what, ERRORS.get(rc, rc), lib().pt_last_error(self.ctx).decode()))
+            err = PtError("%s: %s (%s)" % (what, ERRORS.get(rc, rc), lib().pt_last_error(self.ctx).decode()))
+            err.code = rc
+            raise err
         return rc
 
     def sync(self):
@@ -177,6 +185,30 @@ class Engine:
         self.check(rc, "pt_canvas_encode_jpeg_opt")
         self._jpeg_capacity = max(cap, size.value)
         return bytes(memoryview(buf)[:size.value])
+
+    def encode_canvas_jpeg_begin(self, quality=90, subsampling=0, optimize=False):
+        """MI355X extension (pt_canvas_encode_jpeg_begin): encode_canvas_jpeg without the host wait. Everything is
+        enqueued behind the draws so far and the call returns a Job; its result() is the file the synchronous call
+        would have returned now, whatever is drawn in between. At most JOBS_MAX jobs are pending (PT_ERR_STATE);
+        unlike the synchronous call it runs no deferred screenCopy, so the fused loop stays fused."""
+        job = ctypes.c_void_p(None)
+        self.check(lib().pt_canvas_encode_jpeg_begin(self.ctx, int(quality), int(subsampling), int(optimize),
+                                                     ctypes.byref(job)), "pt_canvas_encode_jpeg_begin")
+        return Job(self, job)
+
+    def read_canvas_begin(self):
+        """MI355X extension (pt_canvas_read_begin): read_canvas without the host wait; the Job's result() is the
+        canvas's RGBA8 bytes, rows bottom-up, as of this call."""
+        job = ctypes.c_void_p(None)
+        self.check(lib().pt_canvas_read_begin(self.ctx, ctypes.byref(job)), "pt_canvas_read_begin")
+        return Job(self, job)
+
+    def job_stats(self):
+        """(jobs begun, finished, of those finished through the slow copy, cancelled) since the engine was created;
+        no device work."""
+        buf = (ctypes.c_uint64 * 4)()
+        self.check(lib().pt_job_stats(self.ctx, buf), "pt_job_stats")
+        return tuple(int(v) for v in buf)
 
     def set_row_partition(self, parts, part):
         self.check(lib().pt_set_row_partition(self.ctx, parts, part), "pt_set_row_partition")
@@ -325,6 +357,50 @@ class Engine:
             self.dispose()
         except Exception:
             pass
+
+
+class Job:
+    """A pending encode or read job of an engine (Engine.encode_canvas_jpeg_begin, read_canvas_begin). done() never
+    blocks; result() waits for this job only and returns its bytes; cancel() gives the slot back without them. The
+    handle is dead after result() or cancel(), and with its engine."""
+
+    def __init__(self, engine, handle):
+        self.engine, self.handle = engine, handle
+
+    def _live(self):
+        if not self.handle or not self.engine.ctx:
+            raise PtError("pt_job: the job was finished or cancelled, or its engine disposed")
+
+    def done(self):
+        self._live()
+        flag = ctypes.c_int(0)
+        self.engine.check(lib().pt_job_poll(self.handle, ctypes.byref(flag)), "pt_job_poll")
+        return flag.value == 1
+
+    def result(self):
+        """The job's bytes. The buffer is sized from the length pt_job_finish reports and the call repeated once
+        (PT_ERR_ARG with the needed length in size leaves the job valid)."""
+        self._live()
+        cap = getattr(self.engine, "_job_capacity", 1 << 16)   # (the engine's last job's, as encode_canvas_jpeg)
+        for _ in range(2):
+            buf = (ctypes.c_uint8 * cap)()
+            size = ctypes.c_size_t(0)
+            rc = lib().pt_job_finish(self.handle, buf, cap, ctypes.byref(size))
+            if rc == 0 or size.value <= cap:
+                break
+            cap = size.value
+        self.engine.check(rc, "pt_job_finish")
+        self.engine._job_capacity = max(cap, size.value)
+        self.handle = None
+        return bytes(memoryview(buf)[:size.value])
+
+    def cancel(self):
+        self._live()
+        self.engine.check(lib().pt_job_cancel(self.handle), "pt_job_cancel")
+        self.handle = None
+
+
+JOBS_MAX = 4   # PT_JOBS_MAX
 
 
 class _Tex:

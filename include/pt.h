@@ -199,6 +199,46 @@ int pt_canvas_encode_jpeg_sub(pt_ctx* ctx, int quality, int subsampling,
  * PT_ERR_ARG also for an optimize other than 0 or 1. */
 int pt_canvas_encode_jpeg_opt(pt_ctx* ctx, int quality, int subsampling, int optimize,
                               uint8_t* dst, size_t capacity, size_t* size);
+/* Encode and read jobs: pt_canvas_encode_jpeg_opt and pt_read_pixels(ctx, NULL, ...) without a host wait, for a
+ * loop that serves every frame and keeps its frames in flight. begin enqueues the whole job on the context's stream
+ * - the encoder's kernels into a device buffer of the job's own that holds the longest stream the canvas can have,
+ * pt_jpeg_ship (or, for a read job, one copy) into pinned host memory, one event - and returns; the host goes on
+ * queueing frames; finish waits for that job's event only, not for the stream.
+ *   bytes    exactly what the synchronous call would have returned at the moment of begin: the same file for the
+ *            same quality, subsampling and optimize, or the same width * height * 4 texels, rows bottom-up. Draws,
+ *            pt_canvas_wrap switches and writes to a wrapped canvas queued later on the same stream do not change
+ *            them. A wrapped canvas must stay alive until the jobs begun on it are done (poll says so, or finish
+ *            or cancel returned).
+ *   begin    makes no blocking HIP call once the buffers for the canvas's size exist; the first job at a size, after
+ *            the canvas grew, or in a slot whose pinned buffer is smaller than the last files, allocates and so may
+ *            wait. Unlike the synchronous calls it does NOT run a deferred screenCopy or a waiting blend
+ *            (pt_fuse_stats does not move): the canvas is written by output passes only, each enqueued when its draw
+ *            call returns, so it is complete in stream order. PT_ERR_ARG with *job NULL for what the synchronous call
+ *            refuses (quality, subsampling, optimize, no canvas yet, a canvas wider or taller than 65535) and for a
+ *            NULL job; PT_ERR_STATE when PT_JOBS_MAX jobs are pending (nothing is queued); PT_ERR_UNSUPPORTED on a
+ *            context of several parts, whose canvas part 0 gathers under events of its own (the synchronous calls
+ *            serve it).
+ *   poll     hipEventQuery of the job's event; never blocks. *done 1 once finish would not wait.
+ *   finish   waits for the job, copies into dst, sets *size and releases the job. Capacity too small: PT_ERR_ARG,
+ *            *size is the length needed, dst is untouched and the job stays valid (call again). The pinned buffer
+ *            is sized from the longest file so far and a quarter; of a file longer than that finish fetches the
+ *            rest from the job's device buffer with a blocking copy of its own and the next jobs get more room
+ *            (pt_job_stats out[2] counts these). NULL, a job already finished or cancelled: PT_ERR_ARG.
+ *   cancel   releases a job without its bytes; waits for its device work, so a slot is never reused under a
+ *            running kernel.
+ * Jobs finish in any order. A handle is one of the context's PT_JOBS_MAX slots: it is dead once finish or cancel
+ * returned PT_OK (a later begin may hand the same pointer out again) and with its context; pt_ctx_destroy waits for
+ * pending jobs and frees them, and pt_canvas_resize waits before it frees the old canvas. A job writes no texture,
+ * not the canvas, and no counter, statistic or timing window other than pt_job_stats: out[0] jobs begun, [1]
+ * finished, [2] of those, finished through the slow copy, [3] cancelled. */
+typedef struct pt_job pt_job;
+#define PT_JOBS_MAX 4
+int pt_canvas_encode_jpeg_begin(pt_ctx* ctx, int quality, int subsampling, int optimize, pt_job** job);
+int pt_canvas_read_begin(pt_ctx* ctx, pt_job** job);              /* the RGBA8 canvas, rows bottom-up */
+int pt_job_poll(pt_job* job, int* done);                          /* never blocks */
+int pt_job_finish(pt_job* job, uint8_t* dst, size_t capacity, size_t* size);
+int pt_job_cancel(pt_job* job);
+int pt_job_stats(pt_ctx* ctx, uint64_t out[4]);  /* begun, finished, finished through the slow copy, cancelled */
 /* Upload rows of a render target (RGBA32F), used to seed the history buffer in tests and to
  * land gathered bands on the root in multi-GPU runs. */
 int pt_write_pixels(pt_ctx* ctx, pt_texture* tex, const void* src, size_t bytes);
