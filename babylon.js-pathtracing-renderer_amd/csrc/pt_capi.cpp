@@ -49,6 +49,7 @@
 #include "pt_devmem.h"
 #include "pt_pairs.h"
 #include "pt_jpeg_enc.h"
+#include "pt_png_enc.h"
 
 extern "C" {
 hipError_t pt_launch_exhaustive(int op, unsigned long long* bad, hipStream_t s);
@@ -66,6 +67,8 @@ hipError_t pt_launch_denoise_var(const pt::DenoiseVarArgs* a, hipStream_t s);
 hipError_t pt_launch_jpeg_measure(const ptj::EncArgs* a, hipStream_t s);
 hipError_t pt_launch_jpeg_pack(const ptj::EncArgs* a, hipStream_t s);
 hipError_t pt_launch_jpeg_ship(const ptj::ShipArgs* a, hipStream_t s);
+hipError_t pt_launch_png_measure(const ptp::PngArgs* a, hipStream_t s);
+hipError_t pt_launch_png_pack(const ptp::PngArgs* a, hipStream_t s);
 hipError_t pt_launch_math_probe(int op, const float* x, const float* y, float* out, int n, hipStream_t s);
 hipError_t pt_launch_persist(int prog, int count, const pt::TraceArgs* a, const pt::WfBufs* w, int tiles_x,
                              unsigned n_wave_tiles, unsigned per_wave, unsigned refill, hipStream_t s);
@@ -176,8 +179,9 @@ struct Dev {
     // three planes, colour[2] + guide (pixels), DENOISE_VAR pt_denoise_variance's, those and var[2] (pixels), JPEG
     // pt_canvas_encode_jpeg's workspace (bytes; pt::JpegLayout), JPEG_OUT the stream it assembles (bytes) and
     // JPEG_OPT what optimised Huffman tables add (bytes; pt::JpegOptLayout). (An encode job's stream buffer is its
-    // slot's own: pt_job::dslot.)
-    enum Slab { WF, LPT, SPILL, RAD, FEAT, CONT, GB, DENOISE, DENOISE_VAR, JPEG, JPEG_OUT, JPEG_OPT, kSlabs };
+    // slot's own: pt_job::dslot.) PNG pt_canvas_encode_png's workspace (bytes; pt::PngLayout) and PNG_OUT the IDATs
+    // it assembles (bytes).
+    enum Slab { WF, LPT, SPILL, RAD, FEAT, CONT, GB, DENOISE, DENOISE_VAR, JPEG, JPEG_OUT, JPEG_OPT, PNG, PNG_OUT, kSlabs };
     DevMem slab[kSlabs];
     pt::WfBufs wf = {};
     size_t wf_pixels = 0, wf_spill = 0;
@@ -1930,6 +1934,55 @@ int dev_canvas_encode_jpeg(Dev* c, int quality, int subsampling, int optimize, u
     HIPCHK(c, hipMemcpyAsync(dst + header, a.out, (size_t)stream, hipMemcpyDeviceToHost, c->stream));
     if (optimize) std::memcpy(dst, head, header);
     else ptj::write_header(dst, c->cw, c->ch, a.qt, hs, vs);   // (while the stream is on its way)
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
+// pt_canvas_encode_png: an observer of the canvas like dev_canvas_encode_jpeg, and laid out like it. The length pass
+// runs first (the filter, a block per chunk, the scan of the IDAT lengths with the Adler-32); the host reads the
+// IDATs' total, sizes the output buffer from it, and the last kernel puts every IDAT in its place, which is copied
+// between the head and the tail the host writes. No timing events, no counters; the canvas is only read.
+int dev_canvas_encode_png(Dev* c, int colour, int filter, uint8_t* dst, size_t capacity, size_t* size)
+{
+    if (!c) return PT_ERR_ARG;
+    if (!dst || !size) return fail(c, PT_ERR_ARG, "pt_canvas_encode_png: dst and size must not be NULL");
+    if (colour < PT_PNG_RGB || colour > PT_PNG_RGBA) return fail(c, PT_ERR_ARG, "pt_canvas_encode_png: colour must be 0 (RGB) or 1 (RGBA)");
+    if (filter < PT_PNG_NONE || filter > PT_PNG_ADAPTIVE) return fail(c, PT_ERR_ARG, "pt_canvas_encode_png: filter must be 0..4 or 5 (adaptive)");
+    if (!c->canvas || c->cw <= 0 || c->ch <= 0) return fail(c, PT_ERR_ARG, "pt_canvas_encode_png: no canvas yet");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = flush_deferred(c)) return rc;
+    const pt::PngLayout L(c->cw, c->ch, colour == PT_PNG_RGBA ? 4 : 3);
+    DevMem& mem = c->slab[Dev::PNG];
+    if (L.bytes > mem.size)
+        if (int rc = mem.grow(c, L.bytes, L.bytes, WAIT_MAIN, false)) return rc;
+    ptp::PngArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.canvas = (const uint32_t*)c->canvas;
+    a.width = c->cw; a.height = c->ch;
+    a.bpp = (int)L.bpp; a.filter = filter;
+    a.row_bytes = L.row_bytes; a.stream = L.stream; a.chunks = L.chunks;
+    a.slot = pt::kPngSlot;
+    char* base = mem.as<char>();
+    a.filtered = (uint8_t*)(base + L.filtered); a.slots = (uint8_t*)(base + L.slots);
+    a.meta = (uint32_t*)(base + L.meta); a.off = (unsigned long long*)(base + L.off);
+    a.total = (unsigned long long*)(base + L.total);
+    HIPCHK(c, pt_launch_png_measure(&a, c->stream));
+    unsigned long long idat = 0;
+    HIPCHK(c, hipMemcpyAsync(&idat, a.total, sizeof(idat), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (idat > L.idat_max()) return fail(c, PT_ERR_STATE, "pt_canvas_encode_png: the IDATs' length is past its bound");
+    *size = pt::kPngHead + (size_t)idat + pt::kPngTail;
+    if (capacity < *size) return fail(c, PT_ERR_ARG, "pt_canvas_encode_png: destination too small");
+    DevMem& out = c->slab[Dev::PNG_OUT];
+    if (idat > out.size) {   // with a quarter of headroom, as the JPEG stream's buffer
+        const size_t room = pt::jpeg_out_room((size_t)idat, L.idat_max());
+        if (int rc = out.grow(c, room, room, WAIT_MAIN, false)) return rc;
+    }
+    a.out = out.as<uint8_t>();
+    HIPCHK(c, pt_launch_png_pack(&a, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dst + pt::kPngHead, a.out, (size_t)idat, hipMemcpyDeviceToHost, c->stream));
+    ptp::write_png_head(dst, c->cw, c->ch, colour);   // (while the IDATs are on their way)
+    ptp::write_png_tail(dst + pt::kPngHead + (size_t)idat);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return PT_OK;
 }

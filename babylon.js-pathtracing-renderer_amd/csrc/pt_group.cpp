@@ -559,6 +559,18 @@ int pt_canvas_encode_jpeg(pt_ctx* c, int quality, uint8_t* dst, size_t capacity,
     return pt_canvas_encode_jpeg_sub(c, quality, PT_JPEG_444, dst, capacity, size);
 }
 
+int pt_canvas_encode_png(pt_ctx* c, int colour, int filter, uint8_t* dst, size_t capacity, size_t* size)
+{
+    if (!c) return PT_ERR_ARG;
+    if (colour < PT_PNG_RGB || colour > PT_PNG_RGBA)   // (before the parts are made to wait)
+        return fail(c, PT_ERR_ARG, "pt_canvas_encode_png: colour must be 0 (RGB) or 1 (RGBA)");
+    if (filter < PT_PNG_NONE || filter > PT_PNG_ADAPTIVE)
+        return fail(c, PT_ERR_ARG, "pt_canvas_encode_png: filter must be 0..4 or 5 (adaptive)");
+    if (c->n() > 1)   // the gathered canvas, as pt_read_pixels: every part's output and the gather first
+        if (int rc = pt_sync(c)) return rc;
+    return take(c, 0, dev_canvas_encode_png(c->parts[0], colour, filter, dst, capacity, size));
+}
+
 // Encode and read jobs: one-part contexts only (a gathered canvas is ordered by events of this layer, and the
 // synchronous calls serve it). A job belongs to its part; the calls that get a job alone find the context through it.
 int pt_canvas_encode_jpeg_begin(pt_ctx* c, int quality, int subsampling, int optimize, pt_job** job)

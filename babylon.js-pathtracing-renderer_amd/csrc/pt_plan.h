@@ -227,6 +227,41 @@ struct JpegOptLayout {
     }
 };
 
+// pt_canvas_encode_png's workspace (pt_png_enc.hip) for a canvas of width x height pixels of bpp 3 or 4 bytes. The
+// filtered stream is height x (1 + bpp width) bytes, cut into chunks of kPngChunk (255 bytes for each lane of a wave;
+// the last one shorter, never empty). Byte offsets: filtered [stream] | slots [chunks x kPngSlot] each chunk's IDAT
+// payload | meta [chunks x 16 B] its payload length, CRC-32 and Adler sums | off [chunks x 8 B] where its IDAT starts
+// behind the file's head | total [8 B] the IDATs' bytes in all.
+// A chunk's payload at most (kPngSlot): zlib stores a block that would not come out shorter, so the block is below
+// the stored form of the chunk's bytes + 5; the first chunk carries the 2-byte zlib header, every chunk but the last
+// the 5 bytes of a full flush's empty stored block, the last the 4 of the Adler-32: chunk + 12 in all, and the slot is
+// the next multiple of 32 past that (the kernel zeroes and copies it in 32-bit words). An IDAT adds 12 bytes of
+// length, type and CRC. All offsets are 64-bit: no canvas size is refused.
+constexpr size_t kPngChunk = 16320;
+constexpr size_t kPngSlot = 16352;
+constexpr size_t kPngHead = 33, kPngTail = 12;   // signature + IHDR; IEND: what the host writes
+struct PngLayout {
+    size_t bpp, row_bytes, stream, chunks;
+    size_t filtered, slots, meta, off, total, bytes;
+    PngLayout(int width, int height, int bytes_per_pixel)
+    {
+        bpp = (size_t)bytes_per_pixel;
+        row_bytes = bpp * (size_t)width;
+        stream = (size_t)height * (1 + row_bytes);
+        chunks = (stream + kPngChunk - 1) / kPngChunk;
+        Carve c;
+        filtered = c.take(stream); slots = c.take(chunks * kPngSlot);
+        meta = c.take(chunks * 16); off = c.take(chunks * 8);
+        total = c.take(8);
+        bytes = c.at;
+    }
+    // the bytes of chunk i, and of its payload at most
+    size_t chunk_bytes(size_t i) const { return i + 1 < chunks ? kPngChunk : stream - (chunks - 1) * kPngChunk; }
+    static constexpr size_t payload_max(size_t chunk_bytes) { return chunk_bytes + 12; }
+    // the IDATs' bytes at most: what no canvas of this size can exceed
+    size_t idat_max() const { return stream + chunks * (12 + 12); }
+};
+
 // Encode and read jobs (pt_canvas_encode_jpeg_begin, pt_canvas_read_begin; pt_capi.cpp): the asynchronous forms of
 // the canvas's observers. A job slot owns a device buffer, JPEG_JOB, that takes the whole stream whatever the pixels
 // (JobLayout::slot_bytes: stream_max() of the canvas under the longer blocks of either choice of tables), so

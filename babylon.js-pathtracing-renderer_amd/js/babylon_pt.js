@@ -24,6 +24,7 @@
 //   effect.setMomentTarget(momentsRT)             -> pt_set_moment_target (extension: accumulated luminance moments)
 //   engine.denoiseVariance(beautyRT, normalRT, albedoRT, momentsRT, dstRT, opts) -> pt_denoise_variance
 //   engine.encodeCanvasJPEG(quality, subsampling, optimize) -> pt_canvas_encode_jpeg_opt (extension: the canvas as a JPEG file)
+//   engine.encodeCanvasPNG(colour, filter) -> pt_canvas_encode_png (extension: the canvas as a PNG file, lossless)
 //   engine.encodeCanvasJPEGBegin(q, s, o) / readCanvasBegin() -> pt_canvas_encode_jpeg_begin / pt_canvas_read_begin
 //                                (extension: the same without a host wait; a job with done(), finish(), cancel())
 'use strict';
@@ -207,6 +208,26 @@ function install(BABYLON, opts) {
       }
       check(this._pt, rc, 'encodeCanvasJPEG');
       this._jpegCapacity = Math.max(buf.length, size);
+      return buf.subarray(0, size);
+    }
+    // MI355X extension (pt_canvas_encode_png): the canvas as a PNG file, lossless, encoded on the device, as a
+    // Buffer. colour 'rgb' (alpha ignored) or 'rgba'; filter 'none', 'sub', 'up', 'average', 'paeth' on every row or
+    // 'adaptive' (per row the least sum of |byte as int8|); the numbers of include/pt.h are taken too. One IDAT per
+    // 16,320 filtered bytes, each what zlib 1.2.11 writes for that chunk under Z_RLE at level 6 with a full flush.
+    encodeCanvasPNG(colour = 'rgb', filter = 'adaptive') {
+      const colours = { rgb: 0, rgba: 1 };
+      const filters = { none: 0, sub: 1, up: 2, average: 3, paeth: 4, adaptive: 5 };
+      const c = typeof colour === 'string' ? colours[colour] : colour | 0;
+      const f = typeof filter === 'string' ? filters[filter] : filter | 0;
+      if (c === undefined || f === undefined) throw new Error('encodeCanvasPNG: unknown colour or filter');
+      let buf = Buffer.allocUnsafe(this._pngCapacity || 65536);
+      let [rc, size] = addon.pt_canvas_encode_png(this._pt, c, f, buf);
+      if (rc !== 0 && size > buf.length) {
+        buf = Buffer.allocUnsafe(size);
+        [rc, size] = addon.pt_canvas_encode_png(this._pt, c, f, buf);
+      }
+      check(this._pt, rc, 'encodeCanvasPNG');
+      this._pngCapacity = Math.max(buf.length, size);
       return buf.subarray(0, size);
     }
     // MI355X extension (pt_canvas_encode_jpeg_begin): encodeCanvasJPEG without the host wait. Everything is queued

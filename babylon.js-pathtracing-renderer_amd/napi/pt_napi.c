@@ -313,6 +313,18 @@ static napi_value CanvasEncodeJpegOpt(napi_env env, napi_callback_info info)
     CHECK(napi_set_element(env, r, 1, num(env, (double)size)));
     return r;
 }
+/* pt_canvas_encode_png(ctx, colour, filter, out: Uint8Array) -> [status, size], as above */
+static napi_value CanvasEncodePng(napi_env env, napi_callback_info info)
+{
+    napi_value a[MAXARGS], r; if (args(env, info, a, 4) < 0) return NULL;
+    size_t cap, size = 0; uint8_t* p = (uint8_t*)bytes_of(env, a[3], &cap);
+    if (!p) { napi_throw_type_error(env, NULL, "typed array expected"); return NULL; }
+    const int rc = pt_canvas_encode_png((pt_ctx*)handle(env, a[0]), i32(env, a[1]), i32(env, a[2]), p, cap, &size);
+    CHECK(napi_create_array_with_length(env, 2, &r));
+    CHECK(napi_set_element(env, r, 0, num(env, rc)));
+    CHECK(napi_set_element(env, r, 1, num(env, (double)size)));
+    return r;
+}
 /* pt_canvas_encode_jpeg_begin(ctx, quality, subsampling, optimize) -> the job (an external), or the status */
 static napi_value CanvasEncodeJpegBegin(napi_env env, napi_callback_info info)
 {
@@ -578,7 +590,7 @@ static napi_value Init(napi_env env, napi_value exports)
         { "pt_render_target_resize", RtResize }, { "pt_texture_size", TexSize }, { "pt_texture_destroy", TexDestroy },
         { "pt_render", Render }, { "pt_read_pixels", ReadPixels }, { "pt_write_pixels", WritePixels },
         { "pt_canvas_encode_jpeg", CanvasEncodeJpeg }, { "pt_canvas_encode_jpeg_sub", CanvasEncodeJpegSub },
-        { "pt_canvas_encode_jpeg_opt", CanvasEncodeJpegOpt },
+        { "pt_canvas_encode_jpeg_opt", CanvasEncodeJpegOpt }, { "pt_canvas_encode_png", CanvasEncodePng },
         { "pt_canvas_encode_jpeg_begin", CanvasEncodeJpegBegin }, { "pt_canvas_read_begin", CanvasReadBegin },
         { "pt_job_poll", JobPoll }, { "pt_job_finish", JobFinish }, { "pt_job_cancel", JobCancel },
         { "pt_job_stats", JobStats },

@@ -39,7 +39,7 @@ SYMBOLS = [
     "pt_texture_create_rgba32f", "pt_texture_create_rgba8", "pt_render_target_create", "pt_render_target_wrap",
     "pt_render_target_resize", "pt_texture_size", "pt_texture_destroy",
     "pt_render", "pt_read_pixels", "pt_canvas_encode_jpeg", "pt_canvas_encode_jpeg_sub", "pt_canvas_encode_jpeg_opt",
-    "pt_canvas_encode_jpeg_begin", "pt_canvas_read_begin", "pt_job_poll", "pt_job_finish", "pt_job_cancel", "pt_job_stats",
+    "pt_canvas_encode_png", "pt_canvas_encode_jpeg_begin", "pt_canvas_read_begin", "pt_job_poll", "pt_job_finish", "pt_job_cancel", "pt_job_stats",
     "pt_write_pixels",
     "pt_set_row_partition", "pt_set_output_partition", "pt_canvas_wrap", "pt_set_backend", "pt_set_bvh_layout", "pt_bvh_layout_used", "pt_set_stream", "pt_texture_device_ptr", "pt_last_render_ms", "pt_timing_begin", "pt_timing_end", "pt_timing_latency",
     "pt_set_counting", "pt_read_counters", "pt_reset_counters", "pt_queue_stats", "pt_cont_stats", "pt_fuse_stats", "pt_set_feature_targets", "pt_denoise", "pt_set_moment_target", "pt_denoise_variance", "pt_math_probe", "pt_math_exhaustive", "pt_bvh_build", "pt_bvh_build_gpu", "pt_jpeg_size", "pt_jpeg_decode_rgba8", "pt_version",
@@ -79,6 +79,7 @@ def lib():
         "pt_canvas_encode_jpeg": ([vp, i32, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)], i32),
         "pt_canvas_encode_jpeg_sub": ([vp, i32, i32, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)], i32),
         "pt_canvas_encode_jpeg_opt": ([vp, i32, i32, i32, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)], i32),
+        "pt_canvas_encode_png": ([vp, i32, i32, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)], i32),
         "pt_canvas_encode_jpeg_begin": ([vp, i32, i32, i32, ctypes.POINTER(vp)], i32),
         "pt_canvas_read_begin": ([vp, ctypes.POINTER(vp)], i32),
         "pt_job_poll": ([vp, ip], i32),
@@ -184,6 +185,30 @@ class Engine:
             cap = size.value
         self.check(rc, "pt_canvas_encode_jpeg_opt")
         self._jpeg_capacity = max(cap, size.value)
+        return bytes(memoryview(buf)[:size.value])
+
+    PNG_COLOURS = {"rgb": 0, "rgba": 1}
+    PNG_FILTERS = {"none": 0, "sub": 1, "up": 2, "average": 3, "paeth": 4, "adaptive": 5}
+
+    def encode_canvas_png(self, colour="rgb", filter="adaptive"):
+        """MI355X extension (pt_canvas_encode_png): the canvas as a PNG file, lossless, encoded on the device. `colour`
+        "rgb" (alpha ignored) or "rgba"; `filter` "none", "sub", "up", "average", "paeth" on every row, or "adaptive"
+        (per row the least sum of |byte as int8|); the numbers of include/pt.h are taken too. One IDAT per 16,320
+        filtered bytes, each what zlib 1.2.11 writes for that chunk under Z_RLE at level 6 with a full flush
+        (tests/png_enc_ref.py). The buffer starts at the last call's length and the call is repeated once when the
+        answer is that it is too small."""
+        colour = self.PNG_COLOURS.get(colour, colour)
+        filter = self.PNG_FILTERS.get(filter, filter)
+        cap = getattr(self, "_png_capacity", 1 << 16)
+        for _ in range(2):
+            buf = (ctypes.c_uint8 * cap)()
+            size = ctypes.c_size_t(0)
+            rc = lib().pt_canvas_encode_png(self.ctx, int(colour), int(filter), buf, cap, ctypes.byref(size))
+            if rc == 0 or size.value <= cap:
+                break
+            cap = size.value
+        self.check(rc, "pt_canvas_encode_png")
+        self._png_capacity = max(cap, size.value)
         return bytes(memoryview(buf)[:size.value])
 
     def encode_canvas_jpeg_begin(self, quality=90, subsampling=0, optimize=False):

@@ -199,6 +199,36 @@ int pt_canvas_encode_jpeg_sub(pt_ctx* ctx, int quality, int subsampling,
  * PT_ERR_ARG also for an optimize other than 0 or 1. */
 int pt_canvas_encode_jpeg_opt(pt_ctx* ctx, int quality, int subsampling, int optimize,
                               uint8_t* dst, size_t capacity, size_t* size);
+/* MI355X extension: the canvas, as pt_read_pixels(ctx, NULL, ...) would return it now, encoded on the device as a
+ * PNG file, lossless: non-interlaced, 8 bits per sample, scanline 0 is canvas row height - 1. A browser's default
+ * canvas serialisation (toBlob() / toDataURL() without a type) is a PNG. The definition is tests/png_enc_ref.py
+ * (numpy and Python's zlib); stage by stage: INTEGRATION.md "Encoding the canvas: PNG".
+ *   colour    PT_PNG_RGB writes colour type 2 and ignores alpha; PT_PNG_RGBA writes colour type 6, alpha as it
+ *             stands. bpp is 3 or 4.
+ *   filter    0..4: that PNG filter type on every row (None, Sub, Up, Average, Paeth). PT_PNG_ADAPTIVE: per row the
+ *             type whose filtered row has the least sum of |byte as int8|, the lowest type on a tie. The filters are
+ *             the PNG specification's: the row above the first is zeros, Average is floor((a + b) / 2) on unsigned
+ *             values, Paeth prefers a when pa <= pb && pa <= pc, then b when pb <= pc.
+ *   stream    height x (1 + bpp width) bytes, row by row: the filter byte, then the filtered bytes.
+ *   deflate   the stream is cut into chunks of 16,320 bytes (the last one shorter, never empty). Chunk i is what zlib
+ *             1.2.11 writes for compressobj(6, DEFLATED, 15, 8, Z_RLE) when it is fed that chunk in one compress()
+ *             call followed by flush(Z_FULL_FLUSH), or flush(Z_FINISH) after the last: one block per chunk (stored,
+ *             fixed or dynamic by zlib's size rule, with zlib's trees), tokens are literals and matches of distance 1
+ *             within runs of equal bytes, runs do not cross chunks; every chunk starts on a byte boundary, a non-final
+ *             one ends in the empty stored block 00 00 FF FF after padding; the two header bytes (78 01) precede the
+ *             first chunk, the last has BFINAL set and is followed by the big-endian Adler-32 of the whole stream.
+ *   file      the signature, IHDR, one IDAT per deflate chunk (so no CRC spans chunks), IEND.
+ * It observes like pt_canvas_encode_jpeg: a deferred copy or blend runs first, a context of several parts encodes
+ * part 0's gathered canvas, the call synchronises, and it writes no texture, not the canvas, and no counter,
+ * statistic or timing window. All offsets are 64-bit and no canvas size is refused. *size receives the file's
+ * length. PT_ERR_ARG: colour or filter out of range, NULL dst or size, no canvas yet, capacity below the file's
+ * length (*size is then the length needed and dst is untouched).
+ * Out of scope: a begin / job form, LZ77 matches beyond distance 1, 16-bit samples, palettes, interlace, ancillary
+ * chunks. */
+enum pt_png_colour { PT_PNG_RGB = 0, PT_PNG_RGBA = 1 };
+enum pt_png_filter { PT_PNG_NONE = 0, PT_PNG_SUB = 1, PT_PNG_UP = 2, PT_PNG_AVERAGE = 3, PT_PNG_PAETH = 4,
+                     PT_PNG_ADAPTIVE = 5 };
+int pt_canvas_encode_png(pt_ctx* ctx, int colour, int filter, uint8_t* dst, size_t capacity, size_t* size);
 /* Encode and read jobs: pt_canvas_encode_jpeg_opt and pt_read_pixels(ctx, NULL, ...) without a host wait, for a
  * loop that serves every frame and keeps its frames in flight. begin enqueues the whole job on the context's stream
  * - the encoder's kernels into a device buffer of the job's own that holds the longest stream the canvas can have,
