@@ -50,6 +50,7 @@
 #include "pt_pairs.h"
 #include "pt_jpeg_enc.h"
 #include "pt_png_enc.h"
+#include "pt_hdr_enc.h"
 
 extern "C" {
 hipError_t pt_launch_exhaustive(int op, unsigned long long* bad, hipStream_t s);
@@ -69,6 +70,7 @@ hipError_t pt_launch_jpeg_pack(const ptj::EncArgs* a, hipStream_t s);
 hipError_t pt_launch_jpeg_ship(const ptj::ShipArgs* a, hipStream_t s);
 hipError_t pt_launch_png_measure(const ptp::PngArgs* a, hipStream_t s);
 hipError_t pt_launch_png_pack(const ptp::PngArgs* a, hipStream_t s);
+hipError_t pt_launch_hdr_encode(const pth::HdrArgs* a, hipStream_t s);
 hipError_t pt_launch_math_probe(int op, const float* x, const float* y, float* out, int n, hipStream_t s);
 hipError_t pt_launch_persist(int prog, int count, const pt::TraceArgs* a, const pt::WfBufs* w, int tiles_x,
                              unsigned n_wave_tiles, unsigned per_wave, unsigned refill, hipStream_t s);
@@ -129,11 +131,15 @@ struct DevFx {
 // slot keeps its buffers and its event from job to job: `dslot` the device buffer pt_jpeg_pack assembles the stream
 // in (pt::JobLayout::slot_bytes of the canvas, so it fits whatever the pixels), `pinned` the host buffer
 // (pt::JobLayout) that pt_jpeg_ship or the read job's copy fills, `ev` recorded behind them.
+enum JobKind { JOB_READ, JOB_JPEG, JOB_PNG, JOB_HDR };
 struct pt_job {
     Dev* dev = nullptr;
     int slot = 0;
     bool pending = false;
-    bool jpeg = false;            // else a read job: the canvas's texels in the stream's place
+    int kind = JOB_READ;          // JOB_READ: the canvas's texels in the stream's place
+    int colour = 0;               // (a PNG job's head)
+    size_t header = 0;            // (an HDR job's)
+    const DevTex* tex = nullptr;  // the render target an HDR job reads: it outlives the job
     int w = 0, h = 0, hs = 1, vs = 1, optimize = 0;
     ptj::QuantTables qt;
     size_t room = 0;              // bytes of the stream (or of the texels) the pinned buffer takes for this job
@@ -180,8 +186,9 @@ struct Dev {
     // pt_canvas_encode_jpeg's workspace (bytes; pt::JpegLayout), JPEG_OUT the stream it assembles (bytes) and
     // JPEG_OPT what optimised Huffman tables add (bytes; pt::JpegOptLayout). (An encode job's stream buffer is its
     // slot's own: pt_job::dslot.) PNG pt_canvas_encode_png's workspace (bytes; pt::PngLayout) and PNG_OUT the IDATs
-    // it assembles (bytes).
-    enum Slab { WF, LPT, SPILL, RAD, FEAT, CONT, GB, DENOISE, DENOISE_VAR, JPEG, JPEG_OUT, JPEG_OPT, PNG, PNG_OUT, kSlabs };
+    // it assembles (bytes). HDR pt_target_encode_hdr's workspace (bytes; pt::HdrLayout) and HDR_OUT the coded scanlines
+    // (bytes: the target's bound, so the encode needs no length from the host).
+    enum Slab { WF, LPT, SPILL, RAD, FEAT, CONT, GB, DENOISE, DENOISE_VAR, JPEG, JPEG_OUT, JPEG_OPT, PNG, PNG_OUT, HDR, HDR_OUT, kSlabs };
     DevMem slab[kSlabs];
     pt::WfBufs wf = {};
     size_t wf_pixels = 0, wf_spill = 0;
@@ -1286,6 +1293,8 @@ int dev_sync(Dev* c)
     return PT_OK;
 }
 
+static void jobs_wait_for(Dev* c, const DevTex* t);
+
 int dev_canvas_resize(Dev* c, int w, int h)
 {
     if (!c || w < 0 || h < 0) return PT_ERR_ARG;
@@ -1432,6 +1441,7 @@ int dev_render_target_resize(DevTex* t, int w, int h)
     if (w == t->w && h == t->h) return PT_OK;
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = flush_deferred(c)) return rc;
+    jobs_wait_for(c, t);   // (an HDR job that reads the old texels)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (t->d) HIPCHK(c, hipFree(t->d));
     t->d = nullptr;
@@ -1457,6 +1467,7 @@ void dev_texture_destroy(DevTex* t)
     const pt::MainPlan& pl = c->plan;
     if ((pl.stale.on && (pl.stale.src == t || pl.stale.dst == t)) || (pl.blend.on && (pl.blend.target == t || pl.blend.prev == t)))
         flush_deferred(c);
+    jobs_wait_for(c, t);   // (an HDR job reads it, a wrapped one included)
     for (auto* fx : c->effects)
         for (auto& kv : fx->samplers)
             if (kv.second == t) kv.second = nullptr;
@@ -1987,6 +1998,70 @@ int dev_canvas_encode_png(Dev* c, int colour, int filter, uint8_t* dst, size_t c
     return PT_OK;
 }
 
+namespace {
+
+// what pt_target_encode_hdr and pt_target_encode_hdr_begin refuse alike
+int hdr_check(Dev* c, const DevTex* t, float scale)
+{
+    if (!t || t->ctx != c || t->kind != TEX_RT || !t->d || t->w <= 0 || t->h <= 0)
+        return fail(c, PT_ERR_ARG, "pt_target_encode_hdr: tex must be an RGBA32F render target of this context");
+    if (!(std::isfinite(scale) && scale > 0.0f)) return fail(c, PT_ERR_ARG, "pt_target_encode_hdr: scale must be finite and > 0");
+    return PT_OK;
+}
+
+// The whole encode of `t` as it stands on the main stream into `out` (L.out_max bytes), in the shared workspace
+// slab, which grows first where it must; a.total is where the device leaves the length.
+int hdr_encode(Dev* c, const DevTex* t, float scale, const pt::HdrLayout& L, uint8_t* out, pth::HdrArgs& a)
+{
+    DevMem& mem = c->slab[Dev::HDR];
+    if (L.bytes > mem.size)
+        if (int rc = mem.grow(c, L.bytes, L.bytes, WAIT_MAIN, false)) return rc;
+    std::memset(&a, 0, sizeof(a));
+    a.tex = (const float*)t->d;
+    a.width = t->w; a.height = t->h;
+    a.scale = scale;
+    char* base = mem.as<char>();
+    a.planes = (uint8_t*)(base + L.planes); a.starts = (uint16_t*)(base + L.starts);
+    a.runs = (uint32_t*)(base + L.runs); a.len = (uint32_t*)(base + L.len);
+    a.off = (unsigned long long*)(base + L.off); a.total = (unsigned long long*)(base + L.total);
+    a.out = out;
+    HIPCHK(c, pt_launch_hdr_encode(&a, c->stream));
+    return PT_OK;
+}
+
+}  // namespace
+
+// pt_target_encode_hdr: an observer of a render target like dev_read_pixels. The four kernels run into an output
+// slab that holds the target's bound, so the host reads the length once and copies that many bytes behind the
+// header it writes. No timing events, no counters; the target is only read.
+int dev_target_encode_hdr(Dev* c, const DevTex* t, float scale, uint8_t* dst, size_t capacity, size_t* size)
+{
+    if (!c) return PT_ERR_ARG;
+    if (!dst || !size) return fail(c, PT_ERR_ARG, "pt_target_encode_hdr: dst and size must not be NULL");
+    if (int rc = hdr_check(c, t, scale)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = flush_deferred(c)) return rc;
+    const pt::HdrLayout L(t->w, t->h);
+    uint8_t head[pth::kHeaderMax];
+    const size_t header = pth::write_header(head, t->w, t->h);
+    if (header != L.header) return fail(c, PT_ERR_STATE, "pt_target_encode_hdr: the header's length is not the layout's");
+    DevMem& out = c->slab[Dev::HDR_OUT];
+    if (L.out_max > out.size)
+        if (int rc = out.grow(c, L.out_max, L.out_max, WAIT_MAIN, false)) return rc;
+    pth::HdrArgs a;
+    if (int rc = hdr_encode(c, t, scale, L, out.as<uint8_t>(), a)) return rc;
+    unsigned long long coded = 0;
+    HIPCHK(c, hipMemcpyAsync(&coded, a.total, sizeof(coded), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (coded > L.out_max) return fail(c, PT_ERR_STATE, "pt_target_encode_hdr: the scanlines' length is past its bound");
+    *size = header + (size_t)coded;
+    if (capacity < *size) return fail(c, PT_ERR_ARG, "pt_target_encode_hdr: destination too small");
+    HIPCHK(c, hipMemcpyAsync(dst + header, a.out, (size_t)coded, hipMemcpyDeviceToHost, c->stream));
+    std::memcpy(dst, head, header);   // (while the scanlines are on their way)
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
 // ---- encode and read jobs: the two observers of the canvas without a host wait (include/pt.h) ----
 // begin enqueues on the main stream, in stream order behind the output pass that wrote the canvas and before the
 // next one: the length pass, pt_jpeg_pack into the slot's own device buffer, pt_jpeg_ship into the slot's pinned
@@ -2014,6 +2089,33 @@ int job_take(Dev* c, size_t room, pt_job** out)
     return PT_OK;
 }
 
+// the slot's device buffer holds `need` bytes at least: the largest bound of the jobs it has served
+int job_slot_room(Dev* c, pt_job* j, size_t need)
+{
+    if (need > j->dslot.size) {   // (the slot is free; hipFree waits for the device)
+        j->dslot.release();
+        HIPCHK(c, j->dslot.alloc(need));
+        j->dslot.size = need;
+    }
+    return PT_OK;
+}
+
+// a stream in the slot's device buffer, `total` its length on the device (and, for a JPEG with optimised tables,
+// `tables` right behind it), to the pinned buffer (pt_jpeg_ship)
+int job_ship(Dev* c, pt_job* j, const unsigned long long* total, const ptj::OptTables* tables = nullptr)
+{
+    const pt::JobLayout H(j->room);
+    char* host = (char*)j->pinned;
+    ptj::ShipArgs sa;
+    sa.stream = j->dslot.as<uint8_t>(); sa.total = total; sa.tables = tables;
+    sa.room = j->room;
+    sa.host_stream = (uint8_t*)(host + H.stream);
+    sa.host_total = (unsigned long long*)(host + H.result);
+    sa.host_tables = (ptj::OptTables*)(host + H.result + 8);
+    HIPCHK(c, pt_launch_jpeg_ship(&sa, c->stream));
+    return PT_OK;
+}
+
 // the job is enqueued: its event (default flags: the release behind pt_jpeg_ship's stores reaches the host)
 int job_begun(Dev* c, pt_job* j)
 {
@@ -2036,26 +2138,13 @@ int dev_job_begin_jpeg(Dev* c, int quality, int subsampling, int optimize, pt_jo
     const pt::JpegLayout L(c->cw, c->ch, hs, vs, optimize ? pt::kJpegOptBlockBytes : pt::kJpegBlockBytes);
     pt_job* j = nullptr;
     if (int rc = job_take(c, c->jobs.room(L.stream_max()), &j)) return rc;
-    const size_t need = pt::JobLayout::slot_bytes(c->cw, c->ch, hs, vs);
-    if (need > j->dslot.size) {   // (the slot is free; hipFree waits for the device)
-        j->dslot.release();
-        HIPCHK(c, j->dslot.alloc(need));
-        j->dslot.size = need;
-    }
+    if (int rc = job_slot_room(c, j, pt::JobLayout::slot_bytes(c->cw, c->ch, hs, vs))) return rc;
     ptj::EncArgs a;
     if (int rc = jpeg_measure(c, quality, hs, vs, optimize, L, a)) return rc;
     a.out = j->dslot.as<uint8_t>();
     HIPCHK(c, pt_launch_jpeg_pack(&a, c->stream));
-    const pt::JobLayout H(j->room);
-    char* host = (char*)j->pinned;
-    ptj::ShipArgs sa;
-    sa.stream = a.out; sa.total = a.total; sa.tables = optimize ? a.tables : nullptr;
-    sa.room = j->room;
-    sa.host_stream = (uint8_t*)(host + H.stream);
-    sa.host_total = (unsigned long long*)(host + H.result);
-    sa.host_tables = (ptj::OptTables*)(host + H.result + 8);
-    HIPCHK(c, pt_launch_jpeg_ship(&sa, c->stream));
-    j->jpeg = true;
+    if (int rc = job_ship(c, j, a.total, optimize ? a.tables : nullptr)) return rc;
+    j->kind = JOB_JPEG;
     j->w = c->cw; j->h = c->ch; j->hs = hs; j->vs = vs; j->optimize = optimize;
     j->qt = a.qt;
     j->stream_max = L.stream_max();
@@ -2075,11 +2164,87 @@ int dev_job_begin_read(Dev* c, pt_job** job)
     pt_job* j = nullptr;
     if (int rc = job_take(c, bytes, &j)) return rc;
     HIPCHK(c, hipMemcpyAsync((char*)j->pinned + pt::JobLayout(bytes).stream, c->canvas, bytes, hipMemcpyDeviceToHost, c->stream));
-    j->jpeg = false;
+    j->kind = JOB_READ;
     j->w = c->cw; j->h = c->ch;
     if (int rc = job_begun(c, j)) return rc;
     *job = j;
     return PT_OK;
+}
+
+
+// pt_canvas_encode_png_begin: dev_canvas_encode_png's kernels with the IDATs assembled in the slot's device buffer,
+// which holds their bound, so that pt_png_pack needs no length from the host; the head and the tail at finish
+int dev_job_begin_png(Dev* c, int colour, int filter, pt_job** job)
+{
+    if (job) *job = nullptr;
+    if (!c) return PT_ERR_ARG;
+    if (!job) return fail(c, PT_ERR_ARG, "pt_canvas_encode_png_begin: job must not be NULL");
+    if (colour < PT_PNG_RGB || colour > PT_PNG_RGBA) return fail(c, PT_ERR_ARG, "pt_canvas_encode_png: colour must be 0 (RGB) or 1 (RGBA)");
+    if (filter < PT_PNG_NONE || filter > PT_PNG_ADAPTIVE) return fail(c, PT_ERR_ARG, "pt_canvas_encode_png: filter must be 0..4 or 5 (adaptive)");
+    if (!c->canvas || c->cw <= 0 || c->ch <= 0) return fail(c, PT_ERR_ARG, "pt_canvas_encode_png: no canvas yet");
+    HIPCHK(c, hipSetDevice(c->device));
+    const pt::PngLayout L(c->cw, c->ch, colour == PT_PNG_RGBA ? 4 : 3);
+    pt_job* j = nullptr;
+    if (int rc = job_take(c, c->jobs.room(L.idat_max()), &j)) return rc;
+    if (int rc = job_slot_room(c, j, pt::align256(L.idat_max()))) return rc;
+    DevMem& mem = c->slab[Dev::PNG];
+    if (L.bytes > mem.size)
+        if (int rc = mem.grow(c, L.bytes, L.bytes, WAIT_MAIN, false)) return rc;
+    ptp::PngArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.canvas = (const uint32_t*)c->canvas;
+    a.width = c->cw; a.height = c->ch;
+    a.bpp = (int)L.bpp; a.filter = filter;
+    a.row_bytes = L.row_bytes; a.stream = L.stream; a.chunks = L.chunks;
+    a.slot = pt::kPngSlot;
+    char* base = mem.as<char>();
+    a.filtered = (uint8_t*)(base + L.filtered); a.slots = (uint8_t*)(base + L.slots);
+    a.meta = (uint32_t*)(base + L.meta); a.off = (unsigned long long*)(base + L.off);
+    a.total = (unsigned long long*)(base + L.total);
+    a.out = j->dslot.as<uint8_t>();
+    HIPCHK(c, pt_launch_png_measure(&a, c->stream));
+    HIPCHK(c, pt_launch_png_pack(&a, c->stream));
+    if (int rc = job_ship(c, j, a.total)) return rc;
+    j->kind = JOB_PNG;
+    j->w = c->cw; j->h = c->ch; j->colour = colour;
+    j->stream_max = L.idat_max();
+    if (int rc = job_begun(c, j)) return rc;
+    *job = j;
+    return PT_OK;
+}
+
+// pt_target_encode_hdr_begin: dev_target_encode_hdr's kernels into the slot's device buffer. What is deferred is
+// enqueued first (never waited for), so that the target holds what pt_read_pixels would return.
+int dev_job_begin_hdr(Dev* c, const DevTex* t, float scale, pt_job** job)
+{
+    if (job) *job = nullptr;
+    if (!c) return PT_ERR_ARG;
+    if (!job) return fail(c, PT_ERR_ARG, "pt_target_encode_hdr_begin: job must not be NULL");
+    if (int rc = hdr_check(c, t, scale)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const pt::HdrLayout L(t->w, t->h);
+    if (c->jobs.free_slot() < 0) return fail(c, PT_ERR_STATE, "pt_job: PT_JOBS_MAX jobs are pending; finish or cancel one first");
+    if (int rc = flush_deferred(c)) return rc;
+    pt_job* j = nullptr;
+    if (int rc = job_take(c, c->jobs.room(L.out_max), &j)) return rc;
+    if (int rc = job_slot_room(c, j, pt::align256(L.out_max))) return rc;
+    pth::HdrArgs a;
+    if (int rc = hdr_encode(c, t, scale, L, j->dslot.as<uint8_t>(), a)) return rc;
+    if (int rc = job_ship(c, j, a.total)) return rc;
+    j->kind = JOB_HDR;
+    j->w = t->w; j->h = t->h; j->header = L.header;
+    j->tex = t;
+    j->stream_max = L.out_max;
+    if (int rc = job_begun(c, j)) return rc;
+    *job = j;
+    return PT_OK;
+}
+
+// before a render target's memory goes: the jobs that read it (their kernels are on the main stream)
+static void jobs_wait_for(Dev* c, const DevTex* t)
+{
+    for (pt_job& j : c->job)
+        if (j.pending && j.kind == JOB_HDR && j.tex == t && j.ev) hipEventSynchronize(j.ev);
 }
 
 Dev* dev_job_dev(pt_job* j) { return j ? j->dev : nullptr; }
@@ -2110,7 +2275,7 @@ int dev_job_finish(pt_job* j, uint8_t* dst, size_t capacity, size_t* size)
     HIPCHK(c, hipEventSynchronize(j->ev));
     const pt::JobLayout H(j->room);
     const char* host = (const char*)j->pinned;
-    if (!j->jpeg) {
+    if (j->kind == JOB_READ) {
         *size = j->room;
         if (capacity < *size) return fail(c, PT_ERR_ARG, "pt_job_finish: destination too small");
         std::memcpy(dst, host + H.stream, *size);
@@ -2121,9 +2286,15 @@ int dev_job_finish(pt_job* j, uint8_t* dst, size_t capacity, size_t* size)
     const JpegResult* got = (const JpegResult*)(host + H.result);
     const size_t stream = (size_t)got->stream;
     if (got->stream > j->stream_max) return fail(c, PT_ERR_STATE, "pt_job_finish: the stream's length is past its bound");
+    static_assert(ptj::kOptHeaderMax >= pth::kHeaderMax && ptj::kOptHeaderMax >= pt::kPngHead, "");
     uint8_t head[ptj::kOptHeaderMax];
-    size_t header;
-    if (j->optimize) {
+    size_t header, tail = 0;
+    if (j->kind == JOB_PNG) {
+        ptp::write_png_head(head, j->w, j->h, j->colour);
+        header = pt::kPngHead; tail = pt::kPngTail;
+    } else if (j->kind == JOB_HDR) {
+        header = pth::write_header(head, j->w, j->h);
+    } else if (j->optimize) {
         for (int t = 0; t < 4; t++)
             if (ptj::opt_table_symbols(got->tables, t) < 1)
                 return fail(c, PT_ERR_STATE, "pt_job_finish: the device built no Huffman table");
@@ -2131,7 +2302,7 @@ int dev_job_finish(pt_job* j, uint8_t* dst, size_t capacity, size_t* size)
     } else {
         header = ptj::write_header(head, j->w, j->h, j->qt, j->hs, j->vs);
     }
-    *size = header + stream;
+    *size = header + stream + tail;
     if (capacity < *size) return fail(c, PT_ERR_ARG, "pt_job_finish: destination too small");
     const size_t fast = stream < j->room ? stream : j->room;
     if (stream > fast) {   // before dst is written: an error here leaves the job as it was
@@ -2142,6 +2313,7 @@ int dev_job_finish(pt_job* j, uint8_t* dst, size_t capacity, size_t* size)
     }
     std::memcpy(dst, head, header);
     std::memcpy(dst + header, host + H.stream, fast);
+    if (tail) ptp::write_png_tail(dst + header + stream);
     c->jobs.shipped(stream, j->room);
     j->pending = false;
     c->jobs.release(j->slot, false);

@@ -581,6 +581,34 @@ int pt_canvas_encode_jpeg_begin(pt_ctx* c, int quality, int subsampling, int opt
     return take(c, 0, dev_job_begin_jpeg(c->parts[0], quality, subsampling, optimize, job));
 }
 
+int pt_canvas_encode_png_begin(pt_ctx* c, int colour, int filter, pt_job** job)
+{
+    if (job) *job = nullptr;
+    if (!c) return PT_ERR_ARG;
+    if (c->n() > 1) return fail(c, PT_ERR_UNSUPPORTED, "pt_canvas_encode_png_begin needs a one-part context");
+    return take(c, 0, dev_job_begin_png(c->parts[0], colour, filter, job));
+}
+
+// A render target as a Radiance HDR picture: one-part contexts (a part's targets hold its own bands only).
+int pt_target_encode_hdr(pt_ctx* c, const pt_texture* t, float scale, uint8_t* dst, size_t capacity, size_t* size)
+{
+    if (!c) return PT_ERR_ARG;
+    if (!t || t->ctx != c || t->kind != TEX_RT)
+        return fail(c, PT_ERR_ARG, "pt_target_encode_hdr: tex must be an RGBA32F render target of this context");
+    if (c->n() > 1) return fail(c, PT_ERR_UNSUPPORTED, "pt_target_encode_hdr needs a one-part context");
+    return take(c, 0, dev_target_encode_hdr(c->parts[0], t->sub[0], scale, dst, capacity, size));
+}
+
+int pt_target_encode_hdr_begin(pt_ctx* c, const pt_texture* t, float scale, pt_job** job)
+{
+    if (job) *job = nullptr;
+    if (!c) return PT_ERR_ARG;
+    if (!t || t->ctx != c || t->kind != TEX_RT)
+        return fail(c, PT_ERR_ARG, "pt_target_encode_hdr_begin: tex must be an RGBA32F render target of this context");
+    if (c->n() > 1) return fail(c, PT_ERR_UNSUPPORTED, "pt_target_encode_hdr_begin needs a one-part context");
+    return take(c, 0, dev_job_begin_hdr(c->parts[0], t->sub[0], scale, job));
+}
+
 int pt_canvas_read_begin(pt_ctx* c, pt_job** job)
 {
     if (job) *job = nullptr;

@@ -262,12 +262,49 @@ struct PngLayout {
     size_t idat_max() const { return stream + chunks * (12 + 12); }
 };
 
+// pt_target_encode_hdr's workspace (pt_hdr_enc.hip) for a render target of width x height texels. Scanline y of the
+// file is four byte planes (R, G, B, E), plane p = 4 y + k. Byte offsets: planes [4 height x width] | starts
+// [4 height x width x 2 B] the positions where a plane's maximal runs start, in order | runs, len [4 height x 4 B] a
+// plane's runs and its coded bytes | off [4 height x 8 B] where it starts among the coded scanlines | total [8 B]
+// their bytes in all. A flat scanline (width < 8 or > 32767: the texels as they are, 4 B each) needs none of it but
+// total.
+// A coded plane at most (plane_max): a run piece of n >= 4 bytes and a short token of 2 or 3 cost 2 bytes, never
+// more than they stand for; a literal of n <= 128 bytes costs n + 1. Literals shorter than 128 end their stretch,
+// and a stretch ends at a run piece, which saves 2 bytes at least, or at the plane's end: so the plane costs at
+// most width + (the literals of 128) + (one short literal at its end), and the literals hold width bytes at most:
+// width + ceil(width / 128). A coded scanline adds its 4 head bytes. All offsets are 64-bit.
+struct HdrLayout {
+    bool flat;
+    size_t header, row_max, out_max;
+    size_t planes, starts, runs, len, off, total, bytes;
+    static size_t digits(size_t v) { size_t n = 1; while (v >= 10) { v /= 10; n++; } return n; }
+    static size_t plane_max(size_t width) { return width + (width + 127) / 128; }
+    HdrLayout(int width, int height)
+    {
+        const size_t w = (size_t)width, h = (size_t)height;
+        flat = width < 8 || width > 32767;
+        header = 38 + digits(h) + 4 + digits(w) + 1;   // "#?RADIANCE\nFORMAT=32-bit_rle_rgbe\n\n-Y H +X W\n"
+        row_max = flat ? 4 * w : 4 + 4 * plane_max(w);
+        out_max = h * row_max;
+        Carve c;
+        const size_t coded = flat ? 0 : 4 * h;
+        planes = c.take(coded * w); starts = c.take(coded * w * 2);
+        runs = c.take(coded * 4); len = c.take(coded * 4); off = c.take(coded * 8);
+        total = c.take(8);
+        bytes = c.at;
+    }
+    size_t file_max() const { return header + out_max; }
+};
+
 // Encode and read jobs (pt_canvas_encode_jpeg_begin, pt_canvas_read_begin; pt_capi.cpp): the asynchronous forms of
 // the canvas's observers. A job slot owns a device buffer, JPEG_JOB, that takes the whole stream whatever the pixels
 // (JobLayout::slot_bytes: stream_max() of the canvas under the longer blocks of either choice of tables), so
 // pt_jpeg_pack needs no length from the host, and a pinned host buffer that pt_jpeg_ship fills: result
 // [8 B the stream's length | ptj::OptTables, 1088 B] | stream [`room` bytes]. A read job's texels take the place of
 // the stream. Both stream buffers start on 256 B, so the 16-byte lanes of pt_jpeg_ship are aligned on either side.
+// A PNG job's IDATs (PngLayout::idat_max) and an HDR job's coded scanlines (HdrLayout::out_max) take the stream's
+// place too, shipped by the same kernel without tables; the slot's device buffer holds the largest of the bounds of
+// the jobs it has served.
 constexpr int kJobsMax = 4;   // PT_JOBS_MAX
 struct JobLayout {
     static constexpr size_t kResult = 8 + JpegOptLayout::kTables;

@@ -7,9 +7,7 @@
 // tests/png_enc_ref.py: every 16,320-byte chunk of the filtered stream is what zlib 1.2.11 writes for
 // compressobj(6, DEFLATED, 15, 8, Z_RLE) fed that chunk and flushed with Z_FULL_FLUSH (Z_FINISH after the last).
 //
-// Out of scope: a begin / job form (a follow-up can add it to pt_job, where the slot's device buffer would need the
-// larger of the JPEG and PNG bounds), LZ77 matches beyond distance 1, 16-bit samples, palettes, interlace and
-// ancillary chunks.
+// Out of scope: LZ77 matches beyond distance 1, 16-bit samples, palettes, interlace and ancillary chunks.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

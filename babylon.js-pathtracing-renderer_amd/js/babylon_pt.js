@@ -25,6 +25,8 @@
 //   engine.denoiseVariance(beautyRT, normalRT, albedoRT, momentsRT, dstRT, opts) -> pt_denoise_variance
 //   engine.encodeCanvasJPEG(quality, subsampling, optimize) -> pt_canvas_encode_jpeg_opt (extension: the canvas as a JPEG file)
 //   engine.encodeCanvasPNG(colour, filter) -> pt_canvas_encode_png (extension: the canvas as a PNG file, lossless)
+//   engine.encodeTargetHDR(rt, scale)      -> pt_target_encode_hdr (extension: a render target as a Radiance .hdr file)
+//   engine.encodeTargetHDRBegin(rt, scale) / encodeCanvasPNGBegin(colour, filter) -> their job forms
 //   engine.encodeCanvasJPEGBegin(q, s, o) / readCanvasBegin() -> pt_canvas_encode_jpeg_begin / pt_canvas_read_begin
 //                                (extension: the same without a host wait; a job with done(), finish(), cancel())
 'use strict';
@@ -229,6 +231,39 @@ function install(BABYLON, opts) {
       check(this._pt, rc, 'encodeCanvasPNG');
       this._pngCapacity = Math.max(buf.length, size);
       return buf.subarray(0, size);
+    }
+    // MI355X extension (pt_target_encode_hdr): the RGBA32F RenderTargetTexture `rt` times `scale` as a Radiance .hdr
+    // file (RGBE, scanlines run-length coded plane by plane), encoded on the device, as a Buffer: the accumulation
+    // with scale = 1 / sample count, a denoised frame, a feature buffer. decodeHDR reads it back.
+    encodeTargetHDR(rt, scale = 1.0) {
+      const t = rt ? rt._pt : null;
+      let buf = Buffer.allocUnsafe(this._hdrCapacity || 65536);
+      let [rc, size] = addon.pt_target_encode_hdr(this._pt, t, +scale, buf);
+      if (rc !== 0 && size > buf.length) {
+        buf = Buffer.allocUnsafe(size);
+        [rc, size] = addon.pt_target_encode_hdr(this._pt, t, +scale, buf);
+      }
+      check(this._pt, rc, 'encodeTargetHDR');
+      this._hdrCapacity = Math.max(buf.length, size);
+      return buf.subarray(0, size);
+    }
+    // MI355X extension (pt_target_encode_hdr_begin): encodeTargetHDR without the host wait; what is deferred is
+    // queued first, never waited for. `rt` must outlive the job.
+    encodeTargetHDRBegin(rt, scale = 1.0) {
+      const h = addon.pt_target_encode_hdr_begin(this._pt, rt ? rt._pt : null, +scale);
+      if (typeof h === 'number') { check(this._pt, h, 'encodeTargetHDRBegin'); return null; }
+      return new Job(this, h);
+    }
+    // MI355X extension (pt_canvas_encode_png_begin): encodeCanvasPNG without the host wait
+    encodeCanvasPNGBegin(colour = 'rgb', filter = 'adaptive') {
+      const colours = { rgb: 0, rgba: 1 };
+      const filters = { none: 0, sub: 1, up: 2, average: 3, paeth: 4, adaptive: 5 };
+      const c = typeof colour === 'string' ? colours[colour] : colour | 0;
+      const f = typeof filter === 'string' ? filters[filter] : filter | 0;
+      if (c === undefined || f === undefined) throw new Error('encodeCanvasPNGBegin: unknown colour or filter');
+      const h = addon.pt_canvas_encode_png_begin(this._pt, c, f);
+      if (typeof h === 'number') { check(this._pt, h, 'encodeCanvasPNGBegin'); return null; }
+      return new Job(this, h);
     }
     // MI355X extension (pt_canvas_encode_jpeg_begin): encodeCanvasJPEG without the host wait. Everything is queued
     // behind the draws so far; the returned job's finish() is the file the synchronous call would have returned

@@ -325,6 +325,36 @@ static napi_value CanvasEncodePng(napi_env env, napi_callback_info info)
     CHECK(napi_set_element(env, r, 1, num(env, (double)size)));
     return r;
 }
+/* pt_target_encode_hdr(ctx, tex, scale, out: Uint8Array) -> [status, size], as above */
+static napi_value TargetEncodeHdr(napi_env env, napi_callback_info info)
+{
+    napi_value a[MAXARGS], r; if (args(env, info, a, 4) < 0) return NULL;
+    size_t cap, size = 0; uint8_t* p = (uint8_t*)bytes_of(env, a[3], &cap);
+    if (!p) { napi_throw_type_error(env, NULL, "typed array expected"); return NULL; }
+    const int rc = pt_target_encode_hdr((pt_ctx*)handle(env, a[0]), (const pt_texture*)handle(env, a[1]), (float)f64(env, a[2]),
+                                        p, cap, &size);
+    CHECK(napi_create_array_with_length(env, 2, &r));
+    CHECK(napi_set_element(env, r, 0, num(env, rc)));
+    CHECK(napi_set_element(env, r, 1, num(env, (double)size)));
+    return r;
+}
+/* pt_target_encode_hdr_begin(ctx, tex, scale) -> the job, or the status */
+static napi_value TargetEncodeHdrBegin(napi_env env, napi_callback_info info)
+{
+    napi_value a[MAXARGS]; if (args(env, info, a, 3) < 0) return NULL;
+    pt_job* job = NULL;
+    const int rc = pt_target_encode_hdr_begin((pt_ctx*)handle(env, a[0]), (const pt_texture*)handle(env, a[1]),
+                                              (float)f64(env, a[2]), &job);
+    return job ? ext(env, job) : num(env, rc);
+}
+/* pt_canvas_encode_png_begin(ctx, colour, filter) -> the job, or the status */
+static napi_value CanvasEncodePngBegin(napi_env env, napi_callback_info info)
+{
+    napi_value a[MAXARGS]; if (args(env, info, a, 3) < 0) return NULL;
+    pt_job* job = NULL;
+    const int rc = pt_canvas_encode_png_begin((pt_ctx*)handle(env, a[0]), i32(env, a[1]), i32(env, a[2]), &job);
+    return job ? ext(env, job) : num(env, rc);
+}
 /* pt_canvas_encode_jpeg_begin(ctx, quality, subsampling, optimize) -> the job (an external), or the status */
 static napi_value CanvasEncodeJpegBegin(napi_env env, napi_callback_info info)
 {
@@ -591,6 +621,8 @@ static napi_value Init(napi_env env, napi_value exports)
         { "pt_render", Render }, { "pt_read_pixels", ReadPixels }, { "pt_write_pixels", WritePixels },
         { "pt_canvas_encode_jpeg", CanvasEncodeJpeg }, { "pt_canvas_encode_jpeg_sub", CanvasEncodeJpegSub },
         { "pt_canvas_encode_jpeg_opt", CanvasEncodeJpegOpt }, { "pt_canvas_encode_png", CanvasEncodePng },
+        { "pt_target_encode_hdr", TargetEncodeHdr }, { "pt_target_encode_hdr_begin", TargetEncodeHdrBegin },
+        { "pt_canvas_encode_png_begin", CanvasEncodePngBegin },
         { "pt_canvas_encode_jpeg_begin", CanvasEncodeJpegBegin }, { "pt_canvas_read_begin", CanvasReadBegin },
         { "pt_job_poll", JobPoll }, { "pt_job_finish", JobFinish }, { "pt_job_cancel", JobCancel },
         { "pt_job_stats", JobStats },

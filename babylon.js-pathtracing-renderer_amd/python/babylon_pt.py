@@ -39,7 +39,7 @@ SYMBOLS = [
     "pt_texture_create_rgba32f", "pt_texture_create_rgba8", "pt_render_target_create", "pt_render_target_wrap",
     "pt_render_target_resize", "pt_texture_size", "pt_texture_destroy",
     "pt_render", "pt_read_pixels", "pt_canvas_encode_jpeg", "pt_canvas_encode_jpeg_sub", "pt_canvas_encode_jpeg_opt",
-    "pt_canvas_encode_png", "pt_canvas_encode_jpeg_begin", "pt_canvas_read_begin", "pt_job_poll", "pt_job_finish", "pt_job_cancel", "pt_job_stats",
+    "pt_canvas_encode_png", "pt_target_encode_hdr", "pt_canvas_encode_jpeg_begin", "pt_canvas_encode_png_begin", "pt_target_encode_hdr_begin", "pt_canvas_read_begin", "pt_job_poll", "pt_job_finish", "pt_job_cancel", "pt_job_stats",
     "pt_write_pixels",
     "pt_set_row_partition", "pt_set_output_partition", "pt_canvas_wrap", "pt_set_backend", "pt_set_bvh_layout", "pt_bvh_layout_used", "pt_set_stream", "pt_texture_device_ptr", "pt_last_render_ms", "pt_timing_begin", "pt_timing_end", "pt_timing_latency",
     "pt_set_counting", "pt_read_counters", "pt_reset_counters", "pt_queue_stats", "pt_cont_stats", "pt_fuse_stats", "pt_set_feature_targets", "pt_denoise", "pt_set_moment_target", "pt_denoise_variance", "pt_math_probe", "pt_math_exhaustive", "pt_bvh_build", "pt_bvh_build_gpu", "pt_jpeg_size", "pt_jpeg_decode_rgba8", "pt_version",
@@ -82,6 +82,9 @@ def lib():
         "pt_canvas_encode_png": ([vp, i32, i32, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)], i32),
         "pt_canvas_encode_jpeg_begin": ([vp, i32, i32, i32, ctypes.POINTER(vp)], i32),
         "pt_canvas_read_begin": ([vp, ctypes.POINTER(vp)], i32),
+        "pt_target_encode_hdr": ([vp, vp, ctypes.c_float, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)], i32),
+        "pt_canvas_encode_png_begin": ([vp, i32, i32, ctypes.POINTER(vp)], i32),
+        "pt_target_encode_hdr_begin": ([vp, vp, ctypes.c_float, ctypes.POINTER(vp)], i32),
         "pt_job_poll": ([vp, ip], i32),
         "pt_job_finish": ([vp, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)], i32),
         "pt_job_cancel": ([vp], i32), "pt_job_stats": ([vp, ctypes.POINTER(ctypes.c_uint64)], i32),
@@ -210,6 +213,45 @@ class Engine:
         self.check(rc, "pt_canvas_encode_png")
         self._png_capacity = max(cap, size.value)
         return bytes(memoryview(buf)[:size.value])
+
+    def encode_target_hdr(self, tex, scale=1.0):
+        """MI355X extension (pt_target_encode_hdr): the RGBA32F render target `tex` times `scale` as a Radiance .hdr
+        file (RGBE, scanlines run-length coded plane by plane), encoded on the device: the accumulation with
+        scale = 1 / sample count, a denoised frame, a feature buffer. The bytes are tests/hdr_enc_ref.py's; what
+        pt_assets.decode_hdr returns for them is at or below the scaled texels and within 2^-7 of each texel's
+        largest component. The engine keeps one buffer for these calls, grown to the longest file so far (a frame's
+        file is megabytes, and fresh pages every call cost more than the encode); the call is repeated once when the
+        answer is that the buffer is too small."""
+        for _ in range(2):
+            buf = getattr(self, "_hdr_buf", None) or (ctypes.c_uint8 * (1 << 16))()
+            self._hdr_buf = buf
+            size = ctypes.c_size_t(0)
+            rc = lib().pt_target_encode_hdr(self.ctx, tex.handle if tex is not None else None, float(scale), buf,
+                                            len(buf), ctypes.byref(size))
+            if rc == 0 or size.value <= len(buf):
+                break
+            self._hdr_buf = (ctypes.c_uint8 * size.value)()
+        self.check(rc, "pt_target_encode_hdr")
+        return bytes(memoryview(buf)[:size.value])
+
+    def encode_target_hdr_begin(self, tex, scale=1.0):
+        """MI355X extension (pt_target_encode_hdr_begin): encode_target_hdr without the host wait; the Job's result()
+        is the file the synchronous call would have returned now. What is deferred (a screenCopy, a waiting blend) is
+        enqueued first, never waited for. `tex` must outlive the job."""
+        job = ctypes.c_void_p(None)
+        self.check(lib().pt_target_encode_hdr_begin(self.ctx, tex.handle if tex is not None else None, float(scale),
+                                                    ctypes.byref(job)), "pt_target_encode_hdr_begin")
+        return Job(self, job)
+
+    def encode_canvas_png_begin(self, colour="rgb", filter="adaptive"):
+        """MI355X extension (pt_canvas_encode_png_begin): encode_canvas_png without the host wait; the Job's result()
+        is the file the synchronous call would have returned now. Like the JPEG job it runs nothing deferred."""
+        colour = self.PNG_COLOURS.get(colour, colour)
+        filter = self.PNG_FILTERS.get(filter, filter)
+        job = ctypes.c_void_p(None)
+        self.check(lib().pt_canvas_encode_png_begin(self.ctx, int(colour), int(filter), ctypes.byref(job)),
+                   "pt_canvas_encode_png_begin")
+        return Job(self, job)
 
     def encode_canvas_jpeg_begin(self, quality=90, subsampling=0, optimize=False):
         """MI355X extension (pt_canvas_encode_jpeg_begin): encode_canvas_jpeg without the host wait. Everything is
@@ -466,6 +508,10 @@ class RenderTargetTexture(_Tex):
         out = np.zeros((s["height"], s["width"], 4), dtype=np.float32)
         self.engine.check(lib().pt_read_pixels(self.engine.ctx, self.handle, out.ctypes.data, out.nbytes), "read")
         return out
+
+    def encode_hdr(self, scale=1.0):
+        """The target times `scale` as a Radiance .hdr file, encoded on the device (Engine.encode_target_hdr)."""
+        return self.engine.encode_target_hdr(self, scale)
 
     def write(self, arr):
         arr = np.ascontiguousarray(arr, dtype=np.float32)

@@ -223,12 +223,43 @@ int pt_canvas_encode_jpeg_opt(pt_ctx* ctx, int quality, int subsampling, int opt
  * statistic or timing window. All offsets are 64-bit and no canvas size is refused. *size receives the file's
  * length. PT_ERR_ARG: colour or filter out of range, NULL dst or size, no canvas yet, capacity below the file's
  * length (*size is then the length needed and dst is untouched).
- * Out of scope: a begin / job form, LZ77 matches beyond distance 1, 16-bit samples, palettes, interlace, ancillary
- * chunks. */
+ * The job form is pt_canvas_encode_png_begin, below. Out of scope: LZ77 matches beyond distance 1, 16-bit samples,
+ * palettes, interlace, ancillary chunks. */
 enum pt_png_colour { PT_PNG_RGB = 0, PT_PNG_RGBA = 1 };
 enum pt_png_filter { PT_PNG_NONE = 0, PT_PNG_SUB = 1, PT_PNG_UP = 2, PT_PNG_AVERAGE = 3, PT_PNG_PAETH = 4,
                      PT_PNG_ADAPTIVE = 5 };
 int pt_canvas_encode_png(pt_ctx* ctx, int colour, int filter, uint8_t* dst, size_t capacity, size_t* size);
+/* MI355X extension: a render target's linear radiance, as pt_read_pixels(ctx, tex, ...) would return it now, encoded
+ * on the device as a Radiance picture (.hdr, 32-bit_rle_rgbe): at most 4 B per texel and a sliver against the 16 of
+ * the readback, and what pt_assets.decode_hdr and the JS shim decode. tex is an RGBA32F render target of the context
+ * (a wrapped one too); alpha is ignored; scanline 0 is the target's row height - 1. The definition is
+ * tests/hdr_enc_ref.py (numpy); every comparison with it is bytes ==.
+ *   texel     every step one binary32 operation or exact. v = tex.xyz * scale; c_k = v_k > 0 ? min(v_k, cap) : +0 with
+ *             cap = 255 x 2^119, the largest value RGBE holds (NaN, negatives and -0 give +0, +inf gives cap);
+ *             m = max(max(c.x, c.y), c.z). m < 1e-32f: the texel is 0 0 0 0. Otherwise e = ((bits(m) >> 23) & 255) - 126,
+ *             byte k is (int)floor(c_k x 2^(8 - e)), the fourth byte is e + 128: Radiance's setcolr with the factor
+ *             256 / 2^e taken exactly. A decoder returns byte x 2^(E - 136), never above c_k and within m x 2^-7 of it.
+ *   header    "#?RADIANCE\nFORMAT=32-bit_rle_rgbe\n\n-Y H +X W\n", H and W in decimal.
+ *   scanline  W < 8 or W > 32767: flat, the W texels as R G B E. Otherwise 02 02 W>>8 W&255, then the row's R, G, B
+ *             and E planes, each coded on its own.
+ *   plane     cut into maximal runs of equal bytes. A run of L bytes yields L / 127 run pieces of 127, then the
+ *             remainder r = L % 127 as a run piece when r >= 4 and as r loose bytes otherwise. A run piece of n bytes
+ *             of value b is 128 + n, b. Consecutive loose bytes form a stretch: one of 2 or 3 equal bytes is
+ *             128 + n, b; any other is cut from its left into literals n, b_1 .. b_n of at most 128 bytes. This is the
+ *             parse of Radiance's own scanline writer (MINRUN 4, counts below 128).
+ *   bound     a coded plane is at most W + ceil(W / 128) bytes, so the file header + H (4 + 4 (W + ceil(W / 128))),
+ *             or header + 4 W H for flat widths.
+ * It observes like pt_read_pixels: a deferred screenCopy or a waiting blend that could change tex runs first, the call
+ * synchronises, and it writes no texture, counter, statistic or timing window. Every stage runs on the context's
+ * stream in context-owned workspace; all offsets are 64-bit. *size receives the file's length. PT_ERR_ARG before any
+ * device work: a NULL ctx, a texture that is NULL, of another context or not a render target, a scale that is not
+ * finite and > 0, NULL dst or size; PT_ERR_ARG also for a capacity below the file's length (*size is then the length
+ * needed and dst is untouched). PT_ERR_UNSUPPORTED on a context of several parts, as pt_denoise.
+ * Out of scope: OpenEXR, XYZE, an EXPOSURE= header line, per-pixel weight normalisation (the caller's scale is the
+ * page's uOneOverSampleCounter), contexts of several parts, byte equality with Radiance's own programs (the reference
+ * file is the definition). */
+int pt_target_encode_hdr(pt_ctx* ctx, const pt_texture* tex, float scale,
+                         uint8_t* dst, size_t capacity, size_t* size);
 /* Encode and read jobs: pt_canvas_encode_jpeg_opt and pt_read_pixels(ctx, NULL, ...) without a host wait, for a
  * loop that serves every frame and keeps its frames in flight. begin enqueues the whole job on the context's stream
  * - the encoder's kernels into a device buffer of the job's own that holds the longest stream the canvas can have,
@@ -260,10 +291,22 @@ int pt_canvas_encode_png(pt_ctx* ctx, int colour, int filter, uint8_t* dst, size
  * returned PT_OK (a later begin may hand the same pointer out again) and with its context; pt_ctx_destroy waits for
  * pending jobs and frees them, and pt_canvas_resize waits before it frees the old canvas. A job writes no texture,
  * not the canvas, and no counter, statistic or timing window other than pt_job_stats: out[0] jobs begun, [1]
- * finished, [2] of those, finished through the slow copy, [3] cancelled. */
+ * finished, [2] of those, finished through the slow copy, [3] cancelled.
+ * pt_canvas_encode_png_begin and pt_target_encode_hdr_begin are the job forms of pt_canvas_encode_png and
+ * pt_target_encode_hdr under the same contract: the synchronous call's bytes at the moment of begin, PT_ERR_ARG with
+ * *job NULL for whatever that call refuses, PT_ERR_STATE with PT_JOBS_MAX pending, PT_ERR_UNSUPPORTED on a context of
+ * several parts; poll, finish, cancel, the pinned buffer's growth and pt_job_stats as above. A slot's device buffer
+ * holds the largest bound among the kinds of job it has served (JPEG stream, PNG IDATs, HDR scanlines); growing it may
+ * wait, like any first job at a size. The PNG job, like the JPEG one, runs nothing deferred. The HDR job must make
+ * tex what pt_read_pixels would return, so it enqueues a deferred screenCopy or a waiting blend first - it never
+ * waits for it - and pt_fuse_stats may therefore move. A render target read by a pending job must outlive it:
+ * pt_render_target_resize and pt_texture_destroy wait for the jobs on that texture, as pt_canvas_resize does for the
+ * canvas; a wrapped target's memory is the caller's to keep alive likewise. */
 typedef struct pt_job pt_job;
 #define PT_JOBS_MAX 4
 int pt_canvas_encode_jpeg_begin(pt_ctx* ctx, int quality, int subsampling, int optimize, pt_job** job);
+int pt_canvas_encode_png_begin(pt_ctx* ctx, int colour, int filter, pt_job** job);
+int pt_target_encode_hdr_begin(pt_ctx* ctx, const pt_texture* tex, float scale, pt_job** job);
 int pt_canvas_read_begin(pt_ctx* ctx, pt_job** job);              /* the RGBA8 canvas, rows bottom-up */
 int pt_job_poll(pt_job* job, int* done);                          /* never blocks */
 int pt_job_finish(pt_job* job, uint8_t* dst, size_t capacity, size_t* size);

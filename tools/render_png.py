@@ -11,7 +11,11 @@ With --denoise the accumulation is also filtered by Engine.denoise (pt_denoise, 
 buffers and drawn by the same screenOutput with the result bound as its accumulation sampler - a plain tone map of
 it; saved beside the plain image as <out>_denoised.png.
 
-usage: render_png.py [--workload dragon|bunny|helmet] [--size WxH] [--frames K] [--features DIR] [--denoise] --out PATH"""
+With --hdr PATH the accumulation itself, scaled by 1 / sample count (the page's uOneOverSampleCounter), is written as
+a Radiance .hdr file encoded on the device (Engine.encode_target_hdr): the linear radiance the PNG is a tone map of.
+
+usage: render_png.py [--workload dragon|bunny|helmet] [--size WxH] [--frames K] [--features DIR] [--denoise]
+                     [--hdr PATH] --out PATH"""
 import argparse
 import os
 import sys
@@ -33,6 +37,7 @@ ap.add_argument("--frames", type=int, default=256)
 ap.add_argument("--out", required=True)
 ap.add_argument("--features", metavar="DIR", help="also save normal.png, albedo.png and id.png there")
 ap.add_argument("--denoise", action="store_true", help="also save the denoised image as <out>_denoised.png")
+ap.add_argument("--hdr", metavar="PATH", help="also save the accumulation / sample count as a Radiance .hdr file")
 a = ap.parse_args()
 W, Hh = (int(v) for v in a.size.lower().split("x"))
 meta = H.stream("hdri_helmet_320x180" if a.workload == "helmet" else "gltf_bunny_1080p")
@@ -60,6 +65,13 @@ dt = time.perf_counter() - t0
 img = e.read_canvas(W, Hh)[::-1, :, :3]          # GL rows bottom-up -> image rows top-down
 from PIL import Image                             # noqa: E402
 Image.fromarray(np.ascontiguousarray(img)).save(a.out)
+if a.hdr:
+    last = H.output_call(p.synth_frame(a.frames - 1) if a.frames else p.meta["frames"][0])
+    one_over_n = float(last["uniforms"]["uOneOverSampleCounter"][1][0])
+    data = p.textures["pathTracingRenderTarget"].encode_hdr(one_over_n)
+    with open(a.hdr, "wb") as f:
+        f.write(data)
+    print("hdr: scale 1/%.0f, %d bytes (%.2f B per texel), saved %s" % (1.0 / one_over_n, len(data), len(data) / (W * Hh), a.hdr))
 if a.features:
     PALETTE = np.array([[0, 0, 0], [230, 25, 75], [60, 180, 75], [255, 225, 25], [0, 130, 200], [245, 130, 48],
                         [145, 30, 180], [70, 240, 240], [240, 50, 230], [210, 245, 60], [250, 190, 212], [0, 128, 128]], np.uint8)
