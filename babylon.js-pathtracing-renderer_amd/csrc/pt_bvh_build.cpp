@@ -3,11 +3,15 @@
 // reference builder, which runs in the page's JavaScript (153 ms for StanfordBunny in Node).
 //
 // The reference works in JavaScript doubles on float32 inputs (the per-triangle AABB array is a
-// Float32Array): box corners are Math.min / Math.max of those inputs (signed zeros as
-// ECMAScript defines them), the split value is the double (min + max) * 0.5 of the node's box, and
-// centroids are compared to it as doubles. Nodes are emitted depth-first, left subtree first; an
-// inner node's right link is filled in when its right child is created. If no axis separates the
-// centroids the list is dealt alternately (even positions left).
+// Float32Array): box corners are folded with Babylon's Vector3.minimizeInPlace / maximizeInPlace
+// (js/BVH_Fast_Builder.js:90-91), which in the vendored build are `x < cur && (cur = x)` and its
+// mirror, from +Infinity / -Infinity, in work-list order. So a NaN bound never enters an inner box,
+// the first of equal extremes stays (-0 and +0 compare equal: the first zero keeps its sign), and
+// an axis whose bounds are all NaN keeps the infinity. The split value is the double
+// (min + max) * 0.5 of the node's box, and centroids are compared to it as doubles. Nodes are
+// emitted depth-first, left subtree first; an inner node's right link is filled in when its right
+// child is created. If no axis separates the centroids the list is dealt alternately (even
+// positions left).
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -16,20 +20,6 @@
 #include "../../include/pt.h"
 
 namespace {
-
-// ECMAScript Math.min / Math.max (NaN wins; -0 < +0)
-double js_min(double a, double b)
-{
-    if (a != a || b != b) return NAN;
-    if (a == 0.0 && b == 0.0) return std::signbit(a) ? a : b;
-    return b < a ? b : a;
-}
-double js_max(double a, double b)
-{
-    if (a != a || b != b) return NAN;
-    if (a == 0.0 && b == 0.0) return std::signbit(a) ? b : a;
-    return a < b ? b : a;
-}
 
 struct FlatNode {
     int idObject;       // triangle, or -1 for an inner node
@@ -73,8 +63,9 @@ struct Builder {
         double mn[3] = { INFINITY, INFINITY, INFINITY }, mx[3] = { -INFINITY, -INFINITY, -INFINITY };
         for (uint32_t k : work)
             for (int a = 0; a < 3; a++) {
-                mn[a] = js_min(mn[a], (double)aabb[9 * (size_t)k + a]);
-                mx[a] = js_max(mx[a], (double)aabb[9 * (size_t)k + 3 + a]);
+                const double lo = (double)aabb[9 * (size_t)k + a], hi = (double)aabb[9 * (size_t)k + 3 + a];
+                if (lo < mn[a]) mn[a] = lo;   // minimizeInPlace: false for a NaN and for an equal zero
+                if (hi > mx[a]) mx[a] = hi;   // maximizeInPlace
             }
         double split[3];
         for (int a = 0; a < 3; a++) split[a] = (mn[a] + mx[a]) * 0.5;   // spatial median

@@ -9,11 +9,20 @@
 // parent's: left = p + 1, right = p + 2 * nLeft. That makes every level of the tree independent
 // work: all runs of one depth are split together.
 //
+// The reference folds a run's box with `x < cur && (cur = x)` and its mirror, from +Infinity /
+// -Infinity, in work-list order (csrc/pt_bvh_build.cpp): a NaN bound never enters, and of equal
+// extremes (-0 == +0 among them) the first in the run stays. In parallel that is, per axis, the
+// least (value, position) pair over the run's non-NaN bounds, the value taken with the two zeros
+// as one: a 64-bit key (value key << 32 | position; ~position for the max) under atomicMin /
+// atomicMax. Runs keep the work list's order through the stable partition, so position order is
+// work-list order. The box value is read back from the winning element, sign of zero included; a
+// key nobody lowered (every bound of the axis NaN) leaves the infinity.
+//
 // Device state, all n-sized: perm (the work list, runs contiguous), runb (each position's run
 // start); per run, indexed by its start b: size, node id, box keys, split, axis counts. One level:
-//   pt_bvh_box     per element: the run's box as order-preserving integer keys (atomicMin/Max,
-//                  one atomic per wave when the wave's lanes share a run) + NaN flags
-//   pt_bvh_split   per run: box -> doubles, split (double), axis order by extent
+//   pt_bvh_box     per element: the run's box as (value, position) keys (64-bit atomicMin/Max,
+//                  one atomic per wave and axis when the wave's lanes share a run)
+//   pt_bvh_split   per run: keys -> the winners' bounds as doubles, split (double), axis order by extent
 //   pt_bvh_count   per element: centroid < split on all three axes (ballot counts per wave)
 //   pt_bvh_choose  per run: the first separating axis (or the alternate deal), the inner node
 //   pt_bvh_flag    per element: goes left?
@@ -32,17 +41,16 @@
 namespace ptb {
 
 constexpr int kBlock = 256;
-constexpr uint32_t kNaN = 0x7fc00000u;   // (float)NAN: what the host builder stores for a NaN bound
+typedef unsigned long long u64;
+constexpr u64 kNoMin = ~0ull, kNoMax = 0ull;   // the folds' starts: above / below every key of a bound
 
-// float -> unsigned key whose unsigned order is the float order with -0 < +0 (NaN kept apart)
+// float (not NaN) -> unsigned key whose unsigned order is the float order, -0 and +0 on one key;
+// -inf is 0x007fffff and +inf 0xff800000, so a bound's 64-bit key is never kNoMin or kNoMax
 __device__ inline uint32_t fkey(float f)
 {
-    const uint32_t u = __float_as_uint(f);
+    uint32_t u = __float_as_uint(f);
+    if (u == 0x80000000u) u = 0u;
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ inline float fkeyInv(uint32_t k)
-{
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
 }
 // (float)(double)x of the host builder: a float -> double -> float round trip (quiets a signalling NaN)
 __device__ inline float viaDouble(float x) { return (float)(double)x; }
@@ -55,9 +63,8 @@ struct Level {
     uint32_t* runb2;
     uint32_t* size;          // per run start: run length (0 = not a run start)
     uint32_t* node;          // per run start: node id
-    uint32_t* kmin;          // [3][n] box keys
-    uint32_t* kmax;
-    uint32_t* knan;          // bit a: a NaN among the mins of axis a; bit 3 + a: among the maxes
+    u64* kmin;               // [3][n] box keys: fkey(min) << 32 | position
+    u64* kmax;               //                  fkey(max) << 32 | ~position
     uint32_t* cnt;           // [3][n] centroid < split counts
     double* split;           // [3][n]
     int* order;              // per run start: the axis order, 3 bits each (a0 | a1 << 2 | a2 << 4)
@@ -80,13 +87,11 @@ __global__ __launch_bounds__(kBlock) void pt_bvh_box(Level L)
     const uint32_t b = in ? L.runb[i] : 0xffffffffu;
     const bool act = in && activeRun(L, b);
     const uint32_t k = act ? L.perm[i] : 0u;
-    uint32_t mn[3], mx[3], nanbits = 0;
+    u64 mn[3], mx[3];   // a NaN bound and an idle lane fold nothing in
     for (int a = 0; a < 3; a++) {
         const float lo = act ? L.aabb[9ull * k + a] : 0.0f, hi = act ? L.aabb[9ull * k + 3 + a] : 0.0f;
-        if (lo != lo) nanbits |= 1u << a;
-        if (hi != hi) nanbits |= 8u << a;
-        mn[a] = (act && lo == lo) ? fkey(lo) : 0xffffffffu;
-        mx[a] = (act && hi == hi) ? fkey(hi) : 0u;
+        mn[a] = (act && lo == lo) ? ((u64)fkey(lo) << 32) | i : kNoMin;
+        mx[a] = (act && hi == hi) ? ((u64)fkey(hi) << 32) | (uint32_t)~i : kNoMax;
     }
     // one atomic per wave when every active lane is in the same run (the upper levels)
     const uint64_t actm = __ballot(act);
@@ -95,35 +100,34 @@ __global__ __launch_bounds__(kBlock) void pt_bvh_box(Level L)
     if (__ballot(act && b != b0) == 0ull) {
         for (int o = 32; o > 0; o >>= 1) {
             for (int a = 0; a < 3; a++) {
-                mn[a] = min(mn[a], (uint32_t)__shfl_xor((int)mn[a], o, 64));
-                mx[a] = max(mx[a], (uint32_t)__shfl_xor((int)mx[a], o, 64));
+                const u64 n = __shfl_xor(mn[a], o, 64), x = __shfl_xor(mx[a], o, 64);
+                mn[a] = n < mn[a] ? n : mn[a];   // the position is part of the key: ties go to the
+                mx[a] = x > mx[a] ? x : mx[a];   // first in the run here as they do in the atomics
             }
-            nanbits |= (uint32_t)__shfl_xor((int)nanbits, o, 64);
         }
         if (i % 64u == (uint32_t)(__ffsll((long long)actm) - 1)) {
             for (int a = 0; a < 3; a++) {
-                atomicMin(&L.kmin[a * L.n + b0], mn[a]);
-                atomicMax(&L.kmax[a * L.n + b0], mx[a]);
+                if (mn[a] != kNoMin) atomicMin(&L.kmin[(size_t)a * L.n + b0], mn[a]);
+                if (mx[a] != kNoMax) atomicMax(&L.kmax[(size_t)a * L.n + b0], mx[a]);
             }
-            if (nanbits) atomicOr(&L.knan[b0], nanbits);
         }
         return;
     }
     if (!act) return;
     for (int a = 0; a < 3; a++) {
-        atomicMin(&L.kmin[a * L.n + b], mn[a]);
-        atomicMax(&L.kmax[a * L.n + b], mx[a]);
+        if (mn[a] != kNoMin) atomicMin(&L.kmin[(size_t)a * L.n + b], mn[a]);
+        if (mx[a] != kNoMax) atomicMax(&L.kmax[(size_t)a * L.n + b], mx[a]);
     }
-    if (nanbits) atomicOr(&L.knan[b], nanbits);
 }
 
-// the run's box as the host builder's doubles: Math.min / Math.max folds (NaN wins)
+// the run's box as the host builder's doubles: the winning elements' own bounds (a key's low word
+// is the winner's position in perm, below n), or the fold's start where no bound was folded in
 __device__ inline void runBox(const Level& L, uint32_t b, double mn[3], double mx[3])
 {
-    const uint32_t nb = L.knan[b];
     for (int a = 0; a < 3; a++) {
-        mn[a] = (nb >> a) & 1u ? (double)__uint_as_float(kNaN) : (double)fkeyInv(L.kmin[a * L.n + b]);
-        mx[a] = (nb >> (3 + a)) & 1u ? (double)__uint_as_float(kNaN) : (double)fkeyInv(L.kmax[a * L.n + b]);
+        const u64 kn = L.kmin[(size_t)a * L.n + b], kx = L.kmax[(size_t)a * L.n + b];
+        mn[a] = kn == kNoMin ? (double)INFINITY : (double)L.aabb[9ull * L.perm[(uint32_t)kn] + a];
+        mx[a] = kx == kNoMax ? -(double)INFINITY : (double)L.aabb[9ull * L.perm[~(uint32_t)kx] + 3 + a];
     }
 }
 
@@ -239,8 +243,9 @@ __global__ __launch_bounds__(kBlock) void pt_bvh_move(Level L)
 
 __device__ inline void resetRun(const Level& L, uint32_t b)
 {
-    for (int a = 0; a < 3; a++) { L.kmin[a * L.n + b] = 0xffffffffu; L.kmax[a * L.n + b] = 0u; L.cnt[a * L.n + b] = 0u; }
-    L.knan[b] = 0u;
+    for (int a = 0; a < 3; a++) {
+        L.kmin[(size_t)a * L.n + b] = kNoMin; L.kmax[(size_t)a * L.n + b] = kNoMax; L.cnt[a * L.n + b] = 0u;
+    }
 }
 
 __global__ __launch_bounds__(kBlock) void pt_bvh_next(Level L)
@@ -292,15 +297,15 @@ extern "C" int pt_bvh_build_gpu(int device, const float* aabb_in, const uint32_t
     hipStream_t s;
     if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) return PT_ERR_HIP;
     const size_t N = (size_t)n, tri = (size_t)kmax + 1;
-    // one allocation, carved: aabb, work, perm x2, runb x2, size, node, kmin/kmax/cnt [3N],
-    // knan, order, axis, nleft, flag, scan, split [3N] doubles, out, more, scan temp
+    // one allocation, carved: aabb, work, perm x2, runb x2, size, node, kmin/kmax [3N] 64-bit keys,
+    // cnt [3N], order, axis, nleft, flag, scan, split [3N] doubles, out, more, scan temp
     size_t scanTemp = 0;
     hipcub::DeviceScan::ExclusiveSum(nullptr, scanTemp, (uint32_t*)nullptr, (uint32_t*)nullptr, n, s);
     size_t off = 0;
     auto carve = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
     const size_t oAabb = carve(tri * 9 * 4), oWork = carve(N * 4), oPerm = carve(N * 4), oPerm2 = carve(N * 4),
                  oRunb = carve(N * 4), oRunb2 = carve(N * 4), oSize = carve(N * 4), oNode = carve(N * 4),
-                 oKmin = carve(3 * N * 4), oKmax = carve(3 * N * 4), oCnt = carve(3 * N * 4), oKnan = carve(N * 4),
+                 oKmin = carve(3 * N * 8), oKmax = carve(3 * N * 8), oCnt = carve(3 * N * 4),
                  oOrder = carve(N * 4), oAxis = carve(N * 4), oNleft = carve(N * 4), oFlag = carve(N * 4),
                  oScan = carve(N * 4), oSplit = carve(3 * N * 8), oOut = carve((size_t)nodes * 32), oMore = carve(4),
                  oTemp = carve(scanTemp);
@@ -314,7 +319,7 @@ extern "C" int pt_bvh_build_gpu(int device, const float* aabb_in, const uint32_t
     Level L;
     L.aabb = (const float*)at(oAabb);
     L.size = (uint32_t*)at(oSize); L.node = (uint32_t*)at(oNode);
-    L.kmin = (uint32_t*)at(oKmin); L.kmax = (uint32_t*)at(oKmax); L.knan = (uint32_t*)at(oKnan);
+    L.kmin = (u64*)at(oKmin); L.kmax = (u64*)at(oKmax);
     L.cnt = (uint32_t*)at(oCnt); L.split = (double*)at(oSplit); L.order = (int*)at(oOrder); L.axis = (int*)at(oAxis);
     L.nleft = (uint32_t*)at(oNleft); L.flag = (uint32_t*)at(oFlag); L.scan = (const uint32_t*)at(oScan);
     L.out = (float*)at(oOut); L.more = (uint32_t*)at(oMore); L.n = (uint32_t)n;
