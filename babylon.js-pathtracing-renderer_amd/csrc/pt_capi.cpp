@@ -51,6 +51,7 @@
 #include "pt_jpeg_enc.h"
 #include "pt_png_enc.h"
 #include "pt_hdr_enc.h"
+#include "pt_exr_enc.h"
 
 extern "C" {
 hipError_t pt_launch_exhaustive(int op, unsigned long long* bad, hipStream_t s);
@@ -71,6 +72,7 @@ hipError_t pt_launch_jpeg_ship(const ptj::ShipArgs* a, hipStream_t s);
 hipError_t pt_launch_png_measure(const ptp::PngArgs* a, hipStream_t s);
 hipError_t pt_launch_png_pack(const ptp::PngArgs* a, hipStream_t s);
 hipError_t pt_launch_hdr_encode(const pth::HdrArgs* a, hipStream_t s);
+hipError_t pt_launch_exr_encode(const pte::ExrArgs* a, hipStream_t s);
 hipError_t pt_launch_math_probe(int op, const float* x, const float* y, float* out, int n, hipStream_t s);
 hipError_t pt_launch_persist(int prog, int count, const pt::TraceArgs* a, const pt::WfBufs* w, int tiles_x,
                              unsigned n_wave_tiles, unsigned per_wave, unsigned refill, hipStream_t s);
@@ -131,8 +133,12 @@ struct DevFx {
 // slot keeps its buffers and its event from job to job: `dslot` the device buffer pt_jpeg_pack assembles the stream
 // in (pt::JobLayout::slot_bytes of the canvas, so it fits whatever the pixels), `pinned` the host buffer
 // (pt::JobLayout) that pt_jpeg_ship or the read job's copy fills, `ev` recorded behind them.
-enum JobKind { JOB_READ, JOB_JPEG, JOB_PNG, JOB_HDR };
+enum JobKind { JOB_READ, JOB_JPEG, JOB_PNG, JOB_HDR, JOB_EXR };
 struct pt_job {
+    // (an EXR job's) the file's magic and header as written at begin, and the render targets its channels read
+    uint8_t exr_head[pte::kHeaderMax];
+    const DevTex* exr_tex[pte::kChannelsMax] = {};
+    int exr_texs = 0;
     Dev* dev = nullptr;
     int slot = 0;
     bool pending = false;
@@ -187,8 +193,9 @@ struct Dev {
     // JPEG_OPT what optimised Huffman tables add (bytes; pt::JpegOptLayout). (An encode job's stream buffer is its
     // slot's own: pt_job::dslot.) PNG pt_canvas_encode_png's workspace (bytes; pt::PngLayout) and PNG_OUT the IDATs
     // it assembles (bytes). HDR pt_target_encode_hdr's workspace (bytes; pt::HdrLayout) and HDR_OUT the coded scanlines
-    // (bytes: the target's bound, so the encode needs no length from the host).
-    enum Slab { WF, LPT, SPILL, RAD, FEAT, CONT, GB, DENOISE, DENOISE_VAR, JPEG, JPEG_OUT, JPEG_OPT, PNG, PNG_OUT, HDR, HDR_OUT, kSlabs };
+    // (bytes: the target's bound, so the encode needs no length from the host). EXR pt_targets_encode_exr's workspace
+    // (bytes; pt::ExrLayout) and EXR_OUT its offset table and chunks (bytes: the bound, likewise).
+    enum Slab { WF, LPT, SPILL, RAD, FEAT, CONT, GB, DENOISE, DENOISE_VAR, JPEG, JPEG_OUT, JPEG_OPT, PNG, PNG_OUT, HDR, HDR_OUT, EXR, EXR_OUT, kSlabs };
     DevMem slab[kSlabs];
     pt::WfBufs wf = {};
     size_t wf_pixels = 0, wf_spill = 0;
@@ -2062,6 +2069,108 @@ int dev_target_encode_hdr(Dev* c, const DevTex* t, float scale, uint8_t* dst, si
     return PT_OK;
 }
 
+namespace {
+
+// What pt_targets_encode_exr and pt_targets_encode_exr_begin refuse alike, before any device work; then the channels
+// sorted by name into the kernels' arguments, the file's head and the layout's numbers.
+struct ExrPlan {
+    pte::ExrArgs a;
+    uint8_t head[pte::kHeaderMax];
+    size_t header = 0, sample_bytes = 0;
+    int w = 0, h = 0;
+};
+int exr_plan(Dev* c, const DevExrChan* ch, int n, int compression, ExrPlan& p)
+{
+    if (!ch || n < 1 || n > pte::kChannelsMax) return fail(c, PT_ERR_ARG, "pt_targets_encode_exr: 1..PT_EXR_CHANNELS_MAX channels");
+    if (compression != PT_EXR_NONE && compression != PT_EXR_ZIPS && compression != PT_EXR_ZIP)
+        return fail(c, PT_ERR_ARG, "pt_targets_encode_exr: compression must be PT_EXR_NONE, PT_EXR_ZIPS or PT_EXR_ZIP");
+    int order[pte::kChannelsMax];
+    for (int i = 0; i < n; i++) {
+        const DevTex* t = ch[i].tex;
+        if (!t || t->ctx != c || t->kind != TEX_RT || !t->d || t->w <= 0 || t->h <= 0)
+            return fail(c, PT_ERR_ARG, "pt_targets_encode_exr: every tex must be an RGBA32F render target of this context");
+        if (t->w != ch[0].tex->w || t->h != ch[0].tex->h) return fail(c, PT_ERR_ARG, "pt_targets_encode_exr: the textures' sizes differ");
+        if (ch[i].component < 0 || ch[i].component > 3) return fail(c, PT_ERR_ARG, "pt_targets_encode_exr: component must be 0..3");
+        if (ch[i].type != PT_EXR_HALF && ch[i].type != PT_EXR_FLOAT)
+            return fail(c, PT_ERR_ARG, "pt_targets_encode_exr: type must be PT_EXR_HALF or PT_EXR_FLOAT");
+        if (!std::isfinite(ch[i].scale)) return fail(c, PT_ERR_ARG, "pt_targets_encode_exr: scale must be finite");
+        if (!pte::name_ok(ch[i].name))
+            return fail(c, PT_ERR_ARG, "pt_targets_encode_exr: a name is 1..31 bytes, each 0x21..0x7E");
+        order[i] = i;
+    }
+    // strcmp order: the names as unsigned bytes
+    std::sort(order, order + n, [&](int x, int y) { return std::strcmp(ch[x].name, ch[y].name) < 0; });
+    for (int i = 1; i < n; i++)
+        if (std::strcmp(ch[order[i - 1]].name, ch[order[i]].name) == 0)
+            return fail(c, PT_ERR_ARG, "pt_targets_encode_exr: two channels have one name");
+    std::memset(&p.a, 0, sizeof(p.a));
+    pte::HeaderChan hc[pte::kChannelsMax];
+    p.w = ch[0].tex->w; p.h = ch[0].tex->h;
+    unsigned long long at = 0;
+    for (int i = 0; i < n; i++) {
+        const DevExrChan& s = ch[order[i]];
+        pte::ExrChan& d = p.a.ch[i];
+        d.tex = (const float*)s.tex->d; d.component = s.component; d.type = s.type; d.scale = s.scale;
+        d.at = at;
+        at += (unsigned long long)pte::sample_bytes(s.type) * (unsigned long long)p.w;
+        std::strcpy(hc[i].name, s.name);   // (name_ok: 31 bytes at most)
+        hc[i].type = s.type;
+        p.sample_bytes += (size_t)pte::sample_bytes(s.type);
+    }
+    p.header = pte::write_header(p.head, hc, n, p.w, p.h, compression);
+    p.a.channels = n; p.a.width = p.w; p.a.height = p.h; p.a.compression = compression;
+    return PT_OK;
+}
+
+// The whole encode of the channels as they stand on the main stream into `out` (L.out_max bytes), in the shared
+// workspace slab, which grows first where it must; a.total is where the device leaves the length.
+int exr_encode(Dev* c, ExrPlan& p, const pt::ExrLayout& L, uint8_t* out)
+{
+    DevMem& mem = c->slab[Dev::EXR];
+    if (L.bytes > mem.size)
+        if (int rc = mem.grow(c, L.bytes, L.bytes, WAIT_MAIN, false)) return rc;
+    pte::ExrArgs& a = p.a;
+    a.lines = (int)L.lines; a.pieces = (int)L.pieces;
+    a.line = L.line; a.blocks = L.blocks; a.stride = L.stride; a.header = L.header;
+    char* base = mem.as<char>();
+    a.raw = (uint8_t*)(base + L.raw); a.pred = (uint8_t*)(base + L.pred); a.slots = (uint8_t*)(base + L.slots);
+    a.meta = (uint32_t*)(base + L.meta); a.bmeta = (uint32_t*)(base + L.bmeta);
+    a.off = (unsigned long long*)(base + L.off); a.total = (unsigned long long*)(base + L.total);
+    a.out = out;
+    HIPCHK(c, pt_launch_exr_encode(&a, c->stream));
+    return PT_OK;
+}
+
+}  // namespace
+
+// pt_targets_encode_exr: an observer of render targets like dev_target_encode_hdr, and laid out like it. The kernels
+// run into an output slab that holds the file's bound, so the host reads the length once and copies that many bytes
+// behind the head it writes. No timing events, no counters; the targets are only read.
+int dev_targets_encode_exr(Dev* c, const DevExrChan* ch, int n, int compression, uint8_t* dst, size_t capacity, size_t* size)
+{
+    if (!c) return PT_ERR_ARG;
+    if (!dst || !size) return fail(c, PT_ERR_ARG, "pt_targets_encode_exr: dst and size must not be NULL");
+    ExrPlan p;
+    if (int rc = exr_plan(c, ch, n, compression, p)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = flush_deferred(c)) return rc;
+    const pt::ExrLayout L(p.w, p.h, p.sample_bytes, p.header, compression);
+    DevMem& out = c->slab[Dev::EXR_OUT];
+    if (L.out_max > out.size)
+        if (int rc = out.grow(c, L.out_max, L.out_max, WAIT_MAIN, false)) return rc;
+    if (int rc = exr_encode(c, p, L, out.as<uint8_t>())) return rc;
+    unsigned long long coded = 0;
+    HIPCHK(c, hipMemcpyAsync(&coded, p.a.total, sizeof(coded), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (coded > L.out_max) return fail(c, PT_ERR_STATE, "pt_targets_encode_exr: the chunks' length is past its bound");
+    *size = p.header + (size_t)coded;
+    if (capacity < *size) return fail(c, PT_ERR_ARG, "pt_targets_encode_exr: destination too small");
+    HIPCHK(c, hipMemcpyAsync(dst + p.header, p.a.out, (size_t)coded, hipMemcpyDeviceToHost, c->stream));
+    std::memcpy(dst, p.head, p.header);   // (while the chunks are on their way)
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
 // ---- encode and read jobs: the two observers of the canvas without a host wait (include/pt.h) ----
 // begin enqueues on the main stream, in stream order behind the output pass that wrote the canvas and before the
 // next one: the length pass, pt_jpeg_pack into the slot's own device buffer, pt_jpeg_ship into the slot's pinned
@@ -2240,11 +2349,44 @@ int dev_job_begin_hdr(Dev* c, const DevTex* t, float scale, pt_job** job)
     return PT_OK;
 }
 
+// pt_targets_encode_exr_begin: dev_targets_encode_exr's kernels into the slot's device buffer, which grows to the
+// file's bound. What is deferred is enqueued first (never waited for), as the HDR job does; the head is written now
+// and kept with the job, since the caller's channel array need not outlive the call.
+int dev_job_begin_exr(Dev* c, const DevExrChan* ch, int n, int compression, pt_job** job)
+{
+    if (job) *job = nullptr;
+    if (!c) return PT_ERR_ARG;
+    if (!job) return fail(c, PT_ERR_ARG, "pt_targets_encode_exr_begin: job must not be NULL");
+    ExrPlan p;
+    if (int rc = exr_plan(c, ch, n, compression, p)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const pt::ExrLayout L(p.w, p.h, p.sample_bytes, p.header, compression);
+    if (c->jobs.free_slot() < 0) return fail(c, PT_ERR_STATE, "pt_job: PT_JOBS_MAX jobs are pending; finish or cancel one first");
+    if (int rc = flush_deferred(c)) return rc;
+    pt_job* j = nullptr;
+    if (int rc = job_take(c, c->jobs.room(L.out_max), &j)) return rc;
+    if (int rc = job_slot_room(c, j, pt::align256(L.out_max))) return rc;
+    if (int rc = exr_encode(c, p, L, j->dslot.as<uint8_t>())) return rc;
+    if (int rc = job_ship(c, j, p.a.total)) return rc;
+    j->kind = JOB_EXR;
+    j->w = p.w; j->h = p.h; j->header = p.header;
+    std::memcpy(j->exr_head, p.head, p.header);
+    j->exr_texs = n;
+    for (int i = 0; i < n; i++) j->exr_tex[i] = ch[i].tex;
+    j->stream_max = L.out_max;
+    if (int rc = job_begun(c, j)) return rc;
+    *job = j;
+    return PT_OK;
+}
+
 // before a render target's memory goes: the jobs that read it (their kernels are on the main stream)
 static void jobs_wait_for(Dev* c, const DevTex* t)
 {
     for (pt_job& j : c->job)
         if (j.pending && j.kind == JOB_HDR && j.tex == t && j.ev) hipEventSynchronize(j.ev);
+    for (pt_job& j : c->job)
+        for (int i = 0; i < j.exr_texs; i++)
+            if (j.pending && j.kind == JOB_EXR && j.exr_tex[i] == t && j.ev) hipEventSynchronize(j.ev);
 }
 
 Dev* dev_job_dev(pt_job* j) { return j ? j->dev : nullptr; }
@@ -2287,9 +2429,13 @@ int dev_job_finish(pt_job* j, uint8_t* dst, size_t capacity, size_t* size)
     const size_t stream = (size_t)got->stream;
     if (got->stream > j->stream_max) return fail(c, PT_ERR_STATE, "pt_job_finish: the stream's length is past its bound");
     static_assert(ptj::kOptHeaderMax >= pth::kHeaderMax && ptj::kOptHeaderMax >= pt::kPngHead, "");
+    static_assert(ptj::kOptHeaderMax >= pte::kHeaderMax, "");
     uint8_t head[ptj::kOptHeaderMax];
     size_t header, tail = 0;
-    if (j->kind == JOB_PNG) {
+    if (j->kind == JOB_EXR) {
+        header = j->header;
+        std::memcpy(head, j->exr_head, header);
+    } else if (j->kind == JOB_PNG) {
         ptp::write_png_head(head, j->w, j->h, j->colour);
         header = pt::kPngHead; tail = pt::kPngTail;
     } else if (j->kind == JOB_HDR) {

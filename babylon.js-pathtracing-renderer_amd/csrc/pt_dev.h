@@ -76,11 +76,21 @@ int dev_denoise_variance(Dev* c, const DevTex* beauty, const DevTex* normal_id, 
 int dev_canvas_encode_jpeg(Dev* c, int quality, int subsampling, int optimize, uint8_t* dst, size_t capacity, size_t* size);
 int dev_canvas_encode_png(Dev* c, int colour, int filter, uint8_t* dst, size_t capacity, size_t* size);
 int dev_target_encode_hdr(Dev* c, const DevTex* t, float scale, uint8_t* dst, size_t capacity, size_t* size);
+// a pt_exr_channel with its part's texture
+struct DevExrChan {
+    const char* name;
+    const DevTex* tex;
+    int component;
+    float scale;
+    int type;
+};
+int dev_targets_encode_exr(Dev* c, const DevExrChan* ch, int n, int compression, uint8_t* dst, size_t capacity, size_t* size);
 // encode and read jobs (one-part contexts): a pt_job is a slot of its part, valid for the part's lifetime
 int dev_job_begin_jpeg(Dev* c, int quality, int subsampling, int optimize, pt_job** job);
 int dev_job_begin_read(Dev* c, pt_job** job);
 int dev_job_begin_png(Dev* c, int colour, int filter, pt_job** job);
 int dev_job_begin_hdr(Dev* c, const DevTex* t, float scale, pt_job** job);
+int dev_job_begin_exr(Dev* c, const DevExrChan* ch, int n, int compression, pt_job** job);
 int dev_job_poll(pt_job* job, int* done);
 int dev_job_finish(pt_job* job, uint8_t* dst, size_t capacity, size_t* size);
 int dev_job_cancel(pt_job* job);

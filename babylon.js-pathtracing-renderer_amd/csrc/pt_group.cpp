@@ -609,6 +609,43 @@ int pt_target_encode_hdr_begin(pt_ctx* c, const pt_texture* t, float scale, pt_j
     return take(c, 0, dev_job_begin_hdr(c->parts[0], t->sub[0], scale, job));
 }
 
+namespace {
+// the channels with their textures of part 0; what is refused before the number of parts is looked at
+int exr_channels(pt_ctx* c, const pt_exr_channel* ch, int n, DevExrChan* out, const char* who)
+{
+    if (!ch || n < 1 || n > PT_EXR_CHANNELS_MAX)
+        return fail(c, PT_ERR_ARG, std::string(who) + ": 1..PT_EXR_CHANNELS_MAX channels");
+    for (int i = 0; i < n; i++) {
+        const pt_texture* t = ch[i].tex;
+        if (!t || t->ctx != c || t->kind != TEX_RT)
+            return fail(c, PT_ERR_ARG, std::string(who) + ": every tex must be an RGBA32F render target of this context");
+        out[i] = { ch[i].name, t->sub[0], ch[i].component, ch[i].scale, ch[i].type };
+    }
+    return PT_OK;
+}
+}  // namespace
+
+// Render targets as a multi-channel OpenEXR file: one-part contexts, as pt_target_encode_hdr.
+int pt_targets_encode_exr(pt_ctx* c, const pt_exr_channel* ch, int n, int compression, uint8_t* dst, size_t capacity,
+                          size_t* size)
+{
+    if (!c) return PT_ERR_ARG;
+    DevExrChan dc[PT_EXR_CHANNELS_MAX];
+    if (int rc = exr_channels(c, ch, n, dc, "pt_targets_encode_exr")) return rc;
+    if (c->n() > 1) return fail(c, PT_ERR_UNSUPPORTED, "pt_targets_encode_exr needs a one-part context");
+    return take(c, 0, dev_targets_encode_exr(c->parts[0], dc, n, compression, dst, capacity, size));
+}
+
+int pt_targets_encode_exr_begin(pt_ctx* c, const pt_exr_channel* ch, int n, int compression, pt_job** job)
+{
+    if (job) *job = nullptr;
+    if (!c) return PT_ERR_ARG;
+    DevExrChan dc[PT_EXR_CHANNELS_MAX];
+    if (int rc = exr_channels(c, ch, n, dc, "pt_targets_encode_exr_begin")) return rc;
+    if (c->n() > 1) return fail(c, PT_ERR_UNSUPPORTED, "pt_targets_encode_exr_begin needs a one-part context");
+    return take(c, 0, dev_job_begin_exr(c->parts[0], dc, n, compression, job));
+}
+
 int pt_canvas_read_begin(pt_ctx* c, pt_job** job)
 {
     if (job) *job = nullptr;

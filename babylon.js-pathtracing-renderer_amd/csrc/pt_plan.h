@@ -296,6 +296,41 @@ struct HdrLayout {
     size_t file_max() const { return header + out_max; }
 };
 
+// pt_targets_encode_exr's workspace (pt_exr_enc.hip) for targets of width x height texels whose channels take
+// `sample_bytes` bytes per texel in all (2 for a HALF, 4 for a FLOAT channel). A block is `lines` scanlines (1 for
+// NONE and ZIPS, 16 for ZIP; the last block may be shorter) of `line` bytes each; its predicted bytes are cut into
+// pieces of kPngChunk, each a deflate block. Byte offsets: raw, pred [blocks x stride] the blocks' raw and predicted
+// bytes, every block on 64 B | slots [blocks x pieces x kPngSlot] each piece's deflate bytes | meta [blocks x pieces
+// x 16 B] a piece's length, its place in the chunk's data and its Adler sums | bmeta [blocks x 16 B] the chunk's
+// data size, whether it is the stream, the Adler-32 | off [blocks x 8 B] where the chunk starts | total [8 B]. NONE
+// needs total alone: its chunks are written in place.
+// out_max: the offset table and every chunk with its block raw, which is OpenEXR's own rule for a block that does
+// not compress, so no file exceeds header + out_max. All offsets are 64-bit.
+struct ExrLayout {
+    size_t lines, line, blocks, pieces, stride, header, out_max;
+    size_t raw, pred, slots, meta, bmeta, off, total, bytes;
+    ExrLayout(int width, int height, size_t sample_bytes, size_t header_bytes, int compression)
+    {
+        const bool coded = compression != 0;
+        lines = compression == 3 ? 16 : 1;
+        line = (size_t)width * sample_bytes;
+        blocks = ((size_t)height + lines - 1) / lines;
+        const size_t full = (lines < (size_t)height ? lines : (size_t)height) * line;
+        pieces = (full + kPngChunk - 1) / kPngChunk;
+        stride = (full + 63) & ~(size_t)63;
+        header = header_bytes;
+        out_max = blocks * 16 + (size_t)height * line;
+        Carve c;
+        const size_t nb = coded ? blocks : 0;
+        raw = c.take(nb * stride); pred = c.take(nb * stride);
+        slots = c.take(nb * pieces * kPngSlot); meta = c.take(nb * pieces * 16);
+        bmeta = c.take(nb * 16); off = c.take(nb * 8);
+        total = c.take(8);
+        bytes = c.at;
+    }
+    size_t file_max() const { return header + out_max; }
+};
+
 // Encode and read jobs (pt_canvas_encode_jpeg_begin, pt_canvas_read_begin; pt_capi.cpp): the asynchronous forms of
 // the canvas's observers. A job slot owns a device buffer, JPEG_JOB, that takes the whole stream whatever the pixels
 // (JobLayout::slot_bytes: stream_max() of the canvas under the longer blocks of either choice of tables), so

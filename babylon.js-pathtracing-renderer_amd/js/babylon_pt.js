@@ -27,6 +27,8 @@
 //   engine.encodeCanvasPNG(colour, filter) -> pt_canvas_encode_png (extension: the canvas as a PNG file, lossless)
 //   engine.encodeTargetHDR(rt, scale)      -> pt_target_encode_hdr (extension: a render target as a Radiance .hdr file)
 //   engine.encodeTargetHDRBegin(rt, scale) / encodeCanvasPNGBegin(colour, filter) -> their job forms
+//   engine.encodeTargetsEXR(channels, compression) / encodeTargetsEXRBegin(...) -> pt_targets_encode_exr and its job
+//                                (extension: render targets as one multi-channel OpenEXR file)
 //   engine.encodeCanvasJPEGBegin(q, s, o) / readCanvasBegin() -> pt_canvas_encode_jpeg_begin / pt_canvas_read_begin
 //                                (extension: the same without a host wait; a job with done(), finish(), cancel())
 'use strict';
@@ -161,6 +163,17 @@ function install(BABYLON, opts) {
     if (typeof rc === 'number' && rc !== 0) report(what + ': ' + (ERR[rc] || rc) + ' ' + addon.pt_last_error(ctx));
     return rc;
   }
+  // the addon's arguments of pt_targets_encode_exr behind the context: five parallel arrays and the compression
+  function exrArgs(channels, compression) {
+    const types = { half: 1, float: 2 };
+    const compressions = { none: 0, zips: 2, zip: 3 };
+    const z = typeof compression === 'string' ? compressions[compression] : compression | 0;
+    if (z === undefined) throw new Error('encodeTargetsEXR: unknown compression');
+    const list = Array.from(channels || []);
+    return [list.map((c) => String(c.name)), list.map((c) => (c.rt ? c.rt._pt : null)), list.map((c) => c.component | 0),
+      list.map((c) => (c.scale === undefined ? 1.0 : +c.scale)),
+      list.map((c) => (typeof c.type === 'string' ? types[c.type] | 0 : c.type | 0)), z];
+  }
   function ctxOf(sceneOrEngine) {
     if (sceneOrEngine && sceneOrEngine._pt) return sceneOrEngine._pt;
     if (sceneOrEngine && sceneOrEngine.getEngine && sceneOrEngine.getEngine()._pt) return sceneOrEngine.getEngine()._pt;
@@ -252,6 +265,28 @@ function install(BABYLON, opts) {
     encodeTargetHDRBegin(rt, scale = 1.0) {
       const h = addon.pt_target_encode_hdr_begin(this._pt, rt ? rt._pt : null, +scale);
       if (typeof h === 'number') { check(this._pt, h, 'encodeTargetHDRBegin'); return null; }
+      return new Job(this, h);
+    }
+    // MI355X extension (pt_targets_encode_exr): render targets as one multi-channel OpenEXR file, encoded on the
+    // device, as a Buffer. `channels` is an array of { name, rt, component 0..3, scale, type 'half' | 'float' }: each
+    // stores one component of one RGBA32F RenderTargetTexture times its scale; `compression` 'none', 'zips' or 'zip'.
+    encodeTargetsEXR(channels, compression = 'zip') {
+      const a = exrArgs(channels, compression);
+      let buf = Buffer.allocUnsafe(this._exrCapacity || 65536);
+      let [rc, size] = addon.pt_targets_encode_exr(this._pt, ...a, buf);
+      if (rc !== 0 && size > buf.length) {
+        buf = Buffer.allocUnsafe(size);
+        [rc, size] = addon.pt_targets_encode_exr(this._pt, ...a, buf);
+      }
+      check(this._pt, rc, 'encodeTargetsEXR');
+      this._exrCapacity = Math.max(buf.length, size);
+      return buf.subarray(0, size);
+    }
+    // MI355X extension (pt_targets_encode_exr_begin): encodeTargetsEXR without the host wait; what is deferred is
+    // queued first, never waited for. The targets must outlive the job.
+    encodeTargetsEXRBegin(channels, compression = 'zip') {
+      const h = addon.pt_targets_encode_exr_begin(this._pt, ...exrArgs(channels, compression));
+      if (typeof h === 'number') { check(this._pt, h, 'encodeTargetsEXRBegin'); return null; }
       return new Job(this, h);
     }
     // MI355X extension (pt_canvas_encode_png_begin): encodeCanvasPNG without the host wait

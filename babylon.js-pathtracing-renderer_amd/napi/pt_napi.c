@@ -347,6 +347,55 @@ static napi_value TargetEncodeHdrBegin(napi_env env, napi_callback_info info)
                                               (float)f64(env, a[2]), &job);
     return job ? ext(env, job) : num(env, rc);
 }
+/* The channels of pt_targets_encode_exr as five parallel arrays (names, textures, components, scales, types), all
+ * of the names' length, capped one past PT_EXR_CHANNELS_MAX so that the library refuses a longer list itself. */
+static int exr_channels(napi_env env, napi_value* a, pt_exr_channel* ch, char*** names, uint32_t* count)
+{
+    *names = strings(env, a[0], count);
+    if (!*names) { napi_throw_type_error(env, NULL, "array of names expected"); return -1; }
+    const uint32_t n = *count > PT_EXR_CHANNELS_MAX + 1 ? PT_EXR_CHANNELS_MAX + 1 : *count;
+    for (uint32_t i = 0; i < n; i++) {
+        napi_value e[4];
+        for (int k = 0; k < 4; k++) e[k] = NULL;
+        for (int k = 0; k < 4; k++) napi_get_element(env, a[1 + k], i, &e[k]);
+        ch[i].name = (*names)[i];
+        ch[i].tex = (const pt_texture*)handle(env, e[0]);
+        ch[i].component = i32(env, e[1]);
+        ch[i].scale = (float)f64(env, e[2]);
+        ch[i].type = i32(env, e[3]);
+    }
+    return (int)n;
+}
+/* pt_targets_encode_exr(ctx, names[], texs[], components[], scales[], types[], compression, out: Uint8Array)
+ * -> [status, size], as above */
+static napi_value TargetsEncodeExr(napi_env env, napi_callback_info info)
+{
+    napi_value a[MAXARGS], r; if (args(env, info, a, 8) < 0) return NULL;
+    size_t cap, size = 0; uint8_t* p = (uint8_t*)bytes_of(env, a[7], &cap);
+    if (!p) { napi_throw_type_error(env, NULL, "typed array expected"); return NULL; }
+    pt_exr_channel ch[PT_EXR_CHANNELS_MAX + 1]; char** names; uint32_t count;
+    const int n = exr_channels(env, a + 1, ch, &names, &count);
+    if (n < 0) return NULL;
+    const int rc = pt_targets_encode_exr((pt_ctx*)handle(env, a[0]), ch, n, i32(env, a[6]), p, cap, &size);
+    free_strings(names, count);
+    CHECK(napi_create_array_with_length(env, 2, &r));
+    CHECK(napi_set_element(env, r, 0, num(env, rc)));
+    CHECK(napi_set_element(env, r, 1, num(env, (double)size)));
+    return r;
+}
+/* pt_targets_encode_exr_begin(ctx, names[], texs[], components[], scales[], types[], compression) -> the job, or the
+ * status */
+static napi_value TargetsEncodeExrBegin(napi_env env, napi_callback_info info)
+{
+    napi_value a[MAXARGS]; if (args(env, info, a, 7) < 0) return NULL;
+    pt_exr_channel ch[PT_EXR_CHANNELS_MAX + 1]; char** names; uint32_t count;
+    const int n = exr_channels(env, a + 1, ch, &names, &count);
+    if (n < 0) return NULL;
+    pt_job* job = NULL;
+    const int rc = pt_targets_encode_exr_begin((pt_ctx*)handle(env, a[0]), ch, n, i32(env, a[6]), &job);
+    free_strings(names, count);
+    return job ? ext(env, job) : num(env, rc);
+}
 /* pt_canvas_encode_png_begin(ctx, colour, filter) -> the job, or the status */
 static napi_value CanvasEncodePngBegin(napi_env env, napi_callback_info info)
 {
@@ -623,6 +672,7 @@ static napi_value Init(napi_env env, napi_value exports)
         { "pt_canvas_encode_jpeg_opt", CanvasEncodeJpegOpt }, { "pt_canvas_encode_png", CanvasEncodePng },
         { "pt_target_encode_hdr", TargetEncodeHdr }, { "pt_target_encode_hdr_begin", TargetEncodeHdrBegin },
         { "pt_canvas_encode_png_begin", CanvasEncodePngBegin },
+        { "pt_targets_encode_exr", TargetsEncodeExr }, { "pt_targets_encode_exr_begin", TargetsEncodeExrBegin },
         { "pt_canvas_encode_jpeg_begin", CanvasEncodeJpegBegin }, { "pt_canvas_read_begin", CanvasReadBegin },
         { "pt_job_poll", JobPoll }, { "pt_job_finish", JobFinish }, { "pt_job_cancel", JobCancel },
         { "pt_job_stats", JobStats },

@@ -39,11 +39,19 @@ SYMBOLS = [
     "pt_texture_create_rgba32f", "pt_texture_create_rgba8", "pt_render_target_create", "pt_render_target_wrap",
     "pt_render_target_resize", "pt_texture_size", "pt_texture_destroy",
     "pt_render", "pt_read_pixels", "pt_canvas_encode_jpeg", "pt_canvas_encode_jpeg_sub", "pt_canvas_encode_jpeg_opt",
-    "pt_canvas_encode_png", "pt_target_encode_hdr", "pt_canvas_encode_jpeg_begin", "pt_canvas_encode_png_begin", "pt_target_encode_hdr_begin", "pt_canvas_read_begin", "pt_job_poll", "pt_job_finish", "pt_job_cancel", "pt_job_stats",
+    "pt_canvas_encode_png", "pt_target_encode_hdr", "pt_targets_encode_exr", "pt_targets_encode_exr_begin", "pt_canvas_encode_jpeg_begin", "pt_canvas_encode_png_begin", "pt_target_encode_hdr_begin", "pt_canvas_read_begin", "pt_job_poll", "pt_job_finish", "pt_job_cancel", "pt_job_stats",
     "pt_write_pixels",
     "pt_set_row_partition", "pt_set_output_partition", "pt_canvas_wrap", "pt_set_backend", "pt_set_bvh_layout", "pt_bvh_layout_used", "pt_set_stream", "pt_texture_device_ptr", "pt_last_render_ms", "pt_timing_begin", "pt_timing_end", "pt_timing_latency",
     "pt_set_counting", "pt_read_counters", "pt_reset_counters", "pt_queue_stats", "pt_cont_stats", "pt_fuse_stats", "pt_set_feature_targets", "pt_denoise", "pt_set_moment_target", "pt_denoise_variance", "pt_math_probe", "pt_math_exhaustive", "pt_bvh_build", "pt_bvh_build_gpu", "pt_jpeg_size", "pt_jpeg_decode_rgba8", "pt_version",
 ]
+
+
+
+class ExrChannel(ctypes.Structure):
+    """pt_exr_channel (include/pt.h)"""
+    _fields_ = [("name", ctypes.c_char_p), ("tex", ctypes.c_void_p), ("component", ctypes.c_int),
+                ("scale", ctypes.c_float), ("type", ctypes.c_int)]
+
 
 _lib = None
 
@@ -84,6 +92,8 @@ def lib():
         "pt_canvas_read_begin": ([vp, ctypes.POINTER(vp)], i32),
         "pt_target_encode_hdr": ([vp, vp, ctypes.c_float, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)], i32),
         "pt_canvas_encode_png_begin": ([vp, i32, i32, ctypes.POINTER(vp)], i32),
+        "pt_targets_encode_exr": ([vp, ctypes.POINTER(ExrChannel), i32, i32, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)], i32),
+        "pt_targets_encode_exr_begin": ([vp, ctypes.POINTER(ExrChannel), i32, i32, ctypes.POINTER(vp)], i32),
         "pt_target_encode_hdr_begin": ([vp, vp, ctypes.c_float, ctypes.POINTER(vp)], i32),
         "pt_job_poll": ([vp, ip], i32),
         "pt_job_finish": ([vp, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)], i32),
@@ -242,6 +252,66 @@ class Engine:
         self.check(lib().pt_target_encode_hdr_begin(self.ctx, tex.handle if tex is not None else None, float(scale),
                                                     ctypes.byref(job)), "pt_target_encode_hdr_begin")
         return Job(self, job)
+
+    EXR_TYPES = {"half": 1, "float": 2}
+    EXR_COMPRESSIONS = {"none": 0, "zips": 2, "zip": 3}
+
+    def _exr_channels(self, channels):
+        """[(name, tex, component, scale, type)] -> (a pt_exr_channel array, what it points to)"""
+        arr = (ExrChannel * max(len(channels), 1))()
+        names = []
+        for i, (name, tex, component, scale, kind) in enumerate(channels):
+            names.append(name.encode() if isinstance(name, str) else name)
+            arr[i].name = names[-1]
+            arr[i].tex = tex.handle if tex is not None else None
+            arr[i].component = int(component)
+            arr[i].scale = float(scale)
+            arr[i].type = int(self.EXR_TYPES.get(kind, kind))
+        return arr, names
+
+    def encode_targets_exr(self, channels, compression="zip"):
+        """MI355X extension (pt_targets_encode_exr): render targets as one multi-channel OpenEXR file, encoded on
+        the device. `channels` is a list of (name, tex, component 0..3, scale, "half" | "float"): each stores one
+        component of one RGBA32F render target times its scale; `compression` "none", "zips" (a zlib stream per
+        scanline) or "zip" (per 16 scanlines); the numbers of include/pt.h are taken too. The bytes are
+        tests/exr_enc_ref.py's. The engine keeps one buffer for these calls, grown to the longest file so far; the
+        call is repeated once when the answer is that the buffer is too small."""
+        arr, _names = self._exr_channels(channels)
+        compression = self.EXR_COMPRESSIONS.get(compression, compression)
+        for _ in range(2):
+            buf = getattr(self, "_exr_buf", None) or (ctypes.c_uint8 * (1 << 16))()
+            self._exr_buf = buf
+            size = ctypes.c_size_t(0)
+            rc = lib().pt_targets_encode_exr(self.ctx, arr, len(channels), int(compression), buf, len(buf),
+                                             ctypes.byref(size))
+            if rc == 0 or size.value <= len(buf):
+                break
+            self._exr_buf = (ctypes.c_uint8 * size.value)()
+        self.check(rc, "pt_targets_encode_exr")
+        return bytes(memoryview(buf)[:size.value])
+
+    def encode_targets_exr_begin(self, channels, compression="zip"):
+        """MI355X extension (pt_targets_encode_exr_begin): encode_targets_exr without the host wait; the Job's
+        result() is the file the synchronous call would have returned now. What is deferred is enqueued first, never
+        waited for. The textures must outlive the job."""
+        arr, _names = self._exr_channels(channels)
+        compression = self.EXR_COMPRESSIONS.get(compression, compression)
+        job = ctypes.c_void_p(None)
+        self.check(lib().pt_targets_encode_exr_begin(self.ctx, arr, len(channels), int(compression), ctypes.byref(job)),
+                   "pt_targets_encode_exr_begin")
+        return Job(self, job)
+
+    @staticmethod
+    def exr_aov_channels(beauty, normal_id, albedo_weight, weight, type="half"):
+        """The conventional channel list of a frame with its feature buffers, for encode_targets_exr: R G B (the
+        beauty accumulation), albedo.R/G/B and normal.X/Y/Z (the feature sums), each times 1 / weight - the weight
+        albedo_weight.w holds, uniform over a frame's pixels - and id (normal_id.w as it is, a FLOAT channel)."""
+        inv = 1.0 / float(weight)
+        out = [(n, beauty, k, inv, type) for k, n in enumerate(("R", "G", "B"))]
+        out += [("albedo." + n, albedo_weight, k, inv, type) for k, n in enumerate("RGB")]
+        out += [("normal." + n, normal_id, k, inv, type) for k, n in enumerate("XYZ")]
+        out.append(("id", normal_id, 3, 1.0, "float"))
+        return out
 
     def encode_canvas_png_begin(self, colour="rgb", filter="adaptive"):
         """MI355X extension (pt_canvas_encode_png_begin): encode_canvas_png without the host wait; the Job's result()
@@ -512,6 +582,11 @@ class RenderTargetTexture(_Tex):
     def encode_hdr(self, scale=1.0):
         """The target times `scale` as a Radiance .hdr file, encoded on the device (Engine.encode_target_hdr)."""
         return self.engine.encode_target_hdr(self, scale)
+
+    def encode_exr(self, names=("R", "G", "B"), scale=1.0, type="half", compression="zip"):
+        """The target's first len(names) components times `scale` as an OpenEXR file with those channel names,
+        encoded on the device (Engine.encode_targets_exr)."""
+        return self.engine.encode_targets_exr([(n, self, k, scale, type) for k, n in enumerate(names)], compression)
 
     def write(self, arr):
         arr = np.ascontiguousarray(arr, dtype=np.float32)

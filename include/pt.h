@@ -255,11 +255,63 @@ int pt_canvas_encode_png(pt_ctx* ctx, int colour, int filter, uint8_t* dst, size
  * device work: a NULL ctx, a texture that is NULL, of another context or not a render target, a scale that is not
  * finite and > 0, NULL dst or size; PT_ERR_ARG also for a capacity below the file's length (*size is then the length
  * needed and dst is untouched). PT_ERR_UNSUPPORTED on a context of several parts, as pt_denoise.
- * Out of scope: OpenEXR, XYZE, an EXPOSURE= header line, per-pixel weight normalisation (the caller's scale is the
- * page's uOneOverSampleCounter), contexts of several parts, byte equality with Radiance's own programs (the reference
- * file is the definition). */
+ * Out of scope: XYZE, an EXPOSURE= header line, per-pixel weight normalisation (the caller's scale is the page's
+ * uOneOverSampleCounter), contexts of several parts, byte equality with Radiance's own programs (the reference file
+ * is the definition). Negatives, alpha, ids and named channels are pt_targets_encode_exr's, below. */
 int pt_target_encode_hdr(pt_ctx* ctx, const pt_texture* tex, float scale,
                          uint8_t* dst, size_t capacity, size_t* size);
+/* MI355X extension: render targets as one multi-channel OpenEXR file (single-part, scanlines, version 2, short
+ * names), encoded on the device: the beauty accumulation with its feature buffers for a denoiser or a compositor, a
+ * converged render archived without loss, signed normals and object ids that RGBE cannot hold. Channel i stores
+ * component ch[i].component of ch[i].tex times ch[i].scale under ch[i].name as HALF or FLOAT; several channels may
+ * name one texture; all textures have one size, RGBA32F render targets of the context (wrapped ones too). The
+ * definition is tests/exr_enc_ref.py (numpy and zlib); every comparison with it is bytes ==. Little-endian throughout.
+ *   head      76 2F 31 01, 02 00 00 00, then the attributes channels (chlist), compression, dataWindow and
+ *             displayWindow (0, 0, W - 1, H - 1), lineOrder (0), pixelAspectRatio (1), screenWindowCenter (0, 0),
+ *             screenWindowWidth (1), each as name\0 type\0 int32 size, value, then 00. A chlist entry is name\0,
+ *             int32 type, 4 zero bytes (pLinear and reserved), int32 1, int32 1; the list ends with 00. Channels are
+ *             stored sorted by name as unsigned bytes, whatever order ch has. 277 bytes for one channel "R", and
+ *             len(name) + 17 for every other one.
+ *   table     one uint64 per chunk: its offset in the file, in increasing y.
+ *   chunk     int32 y of its first scanline, int32 data size, the data. It covers 1 scanline (PT_EXR_NONE,
+ *             PT_EXR_ZIPS) or 16 (PT_EXR_ZIP), the last one what is left. Scanline y is the targets' row H - 1 - y. The
+ *             block's raw bytes r are, per scanline, per channel in stored order, that channel's W samples.
+ *   sample    v = x * scale, one binary32 multiply with denormals kept; a scale of exactly 1 takes x's bits as they
+ *             are. FLOAT stores v's bits (0x7FC00000 for a NaN when scale is not 1). HALF rounds v to binary16, to
+ *             nearest even, in integer arithmetic: subnormal halves are produced, what rounds past 65504 is +-inf,
+ *             +-0 is kept, every NaN is 0x7E00.
+ *   ZIPS/ZIP  with n the block's bytes and h = n / 2: t[i] = r[2 i], t[h + i] = r[2 i + 1]; p[0] = t[0],
+ *             p[i] = t[i] - t[i - 1] + 128 mod 256. p is deflated as a zlib stream of its own the way
+ *             pt_canvas_encode_png deflates its filtered stream: 78 01, a deflate block (zlib 1.2.11's bytes under
+ *             Z_RLE, level 6) per 16,320-byte piece with a full flush behind each but the last, the Adler-32 of p. A
+ *             stream shorter than n is the chunk's data; otherwise the data is r itself (OpenEXR's rule: a reader
+ *             tells by size == n).
+ *   bound     the head, 8 bytes of table and 8 of chunk head per chunk, and W H times the channels' sample bytes.
+ * The contract is pt_target_encode_hdr's: it observes like pt_read_pixels (a deferred screenCopy or a waiting blend
+ * that could change a named texture runs first), synchronises, writes no texture, counter, statistic or timing window,
+ * runs on the context's stream in context-owned workspace with 64-bit offsets, and under a row partition encodes the
+ * targets as they stand. *size receives the file's length. PT_ERR_ARG before any device work: n outside
+ * 1..PT_EXR_CHANNELS_MAX, a texture that is NULL, of another context or not a render target, sizes that differ, a
+ * component outside 0..3, a type or compression not listed, a scale that is not finite, a name that is NULL, empty,
+ * longer than 31 bytes or holds a byte outside 0x21..0x7E, two equal names, NULL dst or size; PT_ERR_ARG also for a
+ * capacity below the file's length (*size is then the length needed and dst is untouched). PT_ERR_UNSUPPORTED on a
+ * context of several parts. PT_ERR_HIP (invalid value) for a block of 2^31 bytes or more, or more than 2^31 - 1 pieces.
+ * Out of scope: tiles, multi-part and deep files, RLE / PIZ / PXR24 / B44 / DWA, UINT and subsampled channels, long
+ * names, LZ77 matches beyond distance 1, per-pixel weight division (the accumulation's weight is uniform over a
+ * frame, so the caller's scale is 1 / weight), contexts of several parts. No OpenEXR reader has read these files:
+ * the layout is restated from OpenEXR's file-layout document and checked by the reference's own decoder. */
+enum pt_exr_type { PT_EXR_HALF = 1, PT_EXR_FLOAT = 2 };                       /* OpenEXR's pixel-type numbers */
+enum pt_exr_compression { PT_EXR_NONE = 0, PT_EXR_ZIPS = 2, PT_EXR_ZIP = 3 }; /* OpenEXR's numbers */
+#define PT_EXR_CHANNELS_MAX 16
+typedef struct pt_exr_channel {
+    const char* name;        /* 1..31 bytes, each 0x21..0x7E, e.g. "R", "normal.X", "albedo.R", "id" */
+    const pt_texture* tex;   /* an RGBA32F render target of ctx (wrapped ones too) */
+    int component;           /* 0..3 */
+    float scale;             /* finite */
+    int type;                /* pt_exr_type */
+} pt_exr_channel;
+int pt_targets_encode_exr(pt_ctx* ctx, const pt_exr_channel* ch, int n, int compression,
+                          uint8_t* dst, size_t capacity, size_t* size);
 /* Encode and read jobs: pt_canvas_encode_jpeg_opt and pt_read_pixels(ctx, NULL, ...) without a host wait, for a
  * loop that serves every frame and keeps its frames in flight. begin enqueues the whole job on the context's stream
  * - the encoder's kernels into a device buffer of the job's own that holds the longest stream the canvas can have,
@@ -301,12 +353,17 @@ int pt_target_encode_hdr(pt_ctx* ctx, const pt_texture* tex, float scale,
  * tex what pt_read_pixels would return, so it enqueues a deferred screenCopy or a waiting blend first - it never
  * waits for it - and pt_fuse_stats may therefore move. A render target read by a pending job must outlive it:
  * pt_render_target_resize and pt_texture_destroy wait for the jobs on that texture, as pt_canvas_resize does for the
- * canvas; a wrapped target's memory is the caller's to keep alive likewise. */
+ * canvas; a wrapped target's memory is the caller's to keep alive likewise.
+ * pt_targets_encode_exr_begin is pt_targets_encode_exr's job form under the HDR job's contract: it enqueues what is
+ * deferred first and never waits for it, resize and destroy of any texture it names wait for it, the slot's device
+ * buffer grows to the EXR bound, and the file's head is written at begin, so ch and its names need not outlive the
+ * call. */
 typedef struct pt_job pt_job;
 #define PT_JOBS_MAX 4
 int pt_canvas_encode_jpeg_begin(pt_ctx* ctx, int quality, int subsampling, int optimize, pt_job** job);
 int pt_canvas_encode_png_begin(pt_ctx* ctx, int colour, int filter, pt_job** job);
 int pt_target_encode_hdr_begin(pt_ctx* ctx, const pt_texture* tex, float scale, pt_job** job);
+int pt_targets_encode_exr_begin(pt_ctx* ctx, const pt_exr_channel* ch, int n, int compression, pt_job** job);
 int pt_canvas_read_begin(pt_ctx* ctx, pt_job** job);              /* the RGBA8 canvas, rows bottom-up */
 int pt_job_poll(pt_job* job, int* done);                          /* never blocks */
 int pt_job_finish(pt_job* job, uint8_t* dst, size_t capacity, size_t* size);
