@@ -26,6 +26,8 @@
 //                      pending before anything else could observe it).
 // dev_denoise (pt_denoise) is no draw: the à-trous filter's prep and passes (pt_denoise.hip) on the main stream.
 // dev_denoise_variance (pt_denoise_variance) likewise (pt_denoise_var.hip), with a slab of its own.
+// dev_cast_rays (pt_cast_rays) is no draw either: SceneIntersect of an effect's scene on the caller's rays (pt_raycast.hip),
+// synchronous on the main stream, with a slab of its own and no trace in any target, counter or statistic.
 // The main stream is the context's own or the caller's (dev_set_stream); per-draw timing events are off
 // until asked for (pt_last_render_ms, the timing window).
 #include "../../include/pt.h"
@@ -48,6 +50,7 @@
 #include "pt_dev.h"
 #include "pt_devmem.h"
 #include "pt_pairs.h"
+#include "pt_raycast.h"
 #include "pt_jpeg_enc.h"
 #include "pt_png_enc.h"
 #include "pt_hdr_enc.h"
@@ -194,8 +197,9 @@ struct Dev {
     // slot's own: pt_job::dslot.) PNG pt_canvas_encode_png's workspace (bytes; pt::PngLayout) and PNG_OUT the IDATs
     // it assembles (bytes). HDR pt_target_encode_hdr's workspace (bytes; pt::HdrLayout) and HDR_OUT the coded scanlines
     // (bytes: the target's bound, so the encode needs no length from the host). EXR pt_targets_encode_exr's workspace
-    // (bytes; pt::ExrLayout) and EXR_OUT its offset table and chunks (bytes: the bound, likewise).
-    enum Slab { WF, LPT, SPILL, RAD, FEAT, CONT, GB, DENOISE, DENOISE_VAR, JPEG, JPEG_OUT, JPEG_OPT, PNG, PNG_OUT, HDR, HDR_OUT, EXR, EXR_OUT, kSlabs };
+    // (bytes; pt::ExrLayout) and EXR_OUT its offset table and chunks (bytes: the bound, likewise). RAYCAST pt_cast_rays'
+    // staged rays, records and stack slab (lanes; pt::RaycastLayout).
+    enum Slab { WF, LPT, SPILL, RAD, FEAT, CONT, GB, DENOISE, DENOISE_VAR, JPEG, JPEG_OUT, JPEG_OPT, PNG, PNG_OUT, HDR, HDR_OUT, EXR, EXR_OUT, RAYCAST, kSlabs };
     DevMem slab[kSlabs];
     pt::WfBufs wf = {};
     size_t wf_pixels = 0, wf_spill = 0;
@@ -739,35 +743,14 @@ int flush_blend(Dev* c)
     return run_deferred(c, ops);
 }
 
-// A path-tracing draw's arguments from the effect's uniforms and samplers, checked; `mesh`: the program walks a BVH
-// (whose child-pair records are built here when its textures changed)
-int trace_args(DevFx* fx, DevTex* target, pt::TraceArgs& a, bool& mesh)
+// The scene half of a path-tracing effect's arguments, what SceneIntersect reads: SetupScene(), and for a mesh
+// program (`mesh`) the model's matrix and material switches, its data textures, checked, the walk pt_set_bvh_layout
+// selects (the child-pair records are built here when the textures changed) and the material maps. `a` is the
+// caller's, zeroed. Shared by the draws (trace_args) and pt_cast_rays (dev_cast_rays).
+int scene_args(DevFx* fx, pt::TraceArgs& a, bool& mesh)
 {
     Dev* c = fx->ctx;
-    if (!target || target->kind != TEX_RT) return fail(c, PT_ERR_ARG, "path tracing draws need a render target");
-    DevTex* prev = sampler(fx, "previousBuffer");
-    DevTex* bn = sampler(fx, "blueNoiseTexture");
-    if (!prev || prev->kind == TEX_U8 || prev->w != target->w || prev->h != target->h)
-        return fail(c, PT_ERR_STATE, "previousBuffer must be an RGBA32F texture of the target's size");
-    if (!bn || bn->kind != TEX_U8) return fail(c, PT_ERR_STATE, "blueNoiseTexture must be bound (RGBA8)");
-    std::memset(&a, 0, sizeof(a));
-    a.width = target->w;
-    a.height = target->h;
-    a.num_parts = c->num_parts;
-    a.part = c->part;
-    a.res[0] = uf(fx, "uResolution", 0); a.res[1] = uf(fx, "uResolution", 1);
-    a.rnd[0] = uf(fx, "uRandomVec2", 0); a.rnd[1] = uf(fx, "uRandomVec2", 1);
-    a.ulen = uf(fx, "uULen"); a.vlen = uf(fx, "uVLen");
-    a.frame = uf(fx, "uFrameCounter");
-    a.eps = uf(fx, "uEPS_intersect");
-    a.aperture = uf(fx, "uApertureSize");
-    a.focus = uf(fx, "uFocusDistance");
-    a.moving = ui(fx, "uCameraIsMoving");
-    um4(fx, "uCameraMatrix", a.cam);
     setup_scene(fx, a);
-    a.prev = (const float4*)prev->d;
-    a.out = (float4*)target->d;
-    a.bluenoise = tex8(bn);
     mesh = fx->prog == PT_PROG_GLTF || fx->prog == PT_PROG_HDRI || fx->prog == PT_PROG_SKY_MESH;
     if (mesh) {
         DevTex* bvh = sampler(fx, "tAABBTexture");
@@ -802,6 +785,37 @@ int trace_args(DevFx* fx, DevTex* target, pt::TraceArgs& a, bool& mesh)
     }
     a.counters = c->d_counters;
     a.err = c->d_err;
+    return PT_OK;
+}
+
+// A path-tracing draw's arguments from the effect's uniforms and samplers, checked; `mesh`: the program walks a BVH
+int trace_args(DevFx* fx, DevTex* target, pt::TraceArgs& a, bool& mesh)
+{
+    Dev* c = fx->ctx;
+    if (!target || target->kind != TEX_RT) return fail(c, PT_ERR_ARG, "path tracing draws need a render target");
+    DevTex* prev = sampler(fx, "previousBuffer");
+    DevTex* bn = sampler(fx, "blueNoiseTexture");
+    if (!prev || prev->kind == TEX_U8 || prev->w != target->w || prev->h != target->h)
+        return fail(c, PT_ERR_STATE, "previousBuffer must be an RGBA32F texture of the target's size");
+    if (!bn || bn->kind != TEX_U8) return fail(c, PT_ERR_STATE, "blueNoiseTexture must be bound (RGBA8)");
+    std::memset(&a, 0, sizeof(a));
+    a.width = target->w;
+    a.height = target->h;
+    a.num_parts = c->num_parts;
+    a.part = c->part;
+    a.res[0] = uf(fx, "uResolution", 0); a.res[1] = uf(fx, "uResolution", 1);
+    a.rnd[0] = uf(fx, "uRandomVec2", 0); a.rnd[1] = uf(fx, "uRandomVec2", 1);
+    a.ulen = uf(fx, "uULen"); a.vlen = uf(fx, "uVLen");
+    a.frame = uf(fx, "uFrameCounter");
+    a.eps = uf(fx, "uEPS_intersect");
+    a.aperture = uf(fx, "uApertureSize");
+    a.focus = uf(fx, "uFocusDistance");
+    a.moving = ui(fx, "uCameraIsMoving");
+    um4(fx, "uCameraMatrix", a.cam);
+    if (int rc = scene_args(fx, a, mesh)) return rc;
+    a.prev = (const float4*)prev->d;
+    a.out = (float4*)target->d;
+    a.bluenoise = tex8(bn);
 #ifdef PT_SECPROF
     {   // experiment builds: the wave timeline of the last megakernel draw (pt_debug_wave_log)
         static size_t cap = 0;
@@ -2498,6 +2512,63 @@ int dev_math_exhaustive(Dev* c, int op, uint64_t* mismatches)
     unsigned long long h = 0;
     HIPCHK(c, hipMemcpy(&h, d.p, sizeof(h), hipMemcpyDeviceToHost));
     *mismatches = h;
+    return PT_OK;
+}
+
+// pt_cast_rays: checked by the caller (pt_group.cpp) but for the scene, which scene_args checks; then, chunk by chunk
+// (pt::RaycastLayout), the rays staged into the call's slab, pt_raycast, and the records copied back, all on the main
+// stream - behind every draw's path tracing, which the main stream already waits for (draw_mega), so the slab of a
+// query is never a frame's, and a BVH texture written before the call is seen. It observes no render target: what
+// is deferred stays deferred. No timing events, no counters; scene_args' note of the walk the last draw took
+// (pt_bvh_layout_used) is put back.
+// Measurement (tools/raycast_rate.py): with PT_RAYCAST_EVENTS=1 in the environment the kernel launches of a call are
+// bracketed by events, and pt_debug_raycast_ms returns the last call's kernel time (-1: none); unset, no event is
+// recorded.
+static float g_raycast_ms = -1.0f;
+extern "C" __attribute__((visibility("default"))) float pt_debug_raycast_ms(void) { return g_raycast_ms; }
+
+int dev_cast_rays(DevFx* fx, const float* origins, const float* dirs, int n, pt_ray_hit* hits)
+{
+    if (!fx || n < 0 || (n > 0 && (!origins || !dirs || !hits))) return PT_ERR_ARG;
+    if (n == 0) return PT_OK;
+    Dev* c = fx->ctx;
+    HIPCHK(c, hipSetDevice(c->device));
+    pt::TraceArgs a;
+    std::memset(&a, 0, sizeof(a));
+    bool mesh = false;
+    const int used = c->bvh_used;
+    const int rc = scene_args(fx, a, mesh);
+    c->bvh_used = used;
+    if (rc) return rc;
+    const pt::RaycastLayout L((size_t)n);
+    DevMem& mem = c->slab[Dev::RAYCAST];
+    if (L.lanes > mem.size)
+        if (int grc = mem.grow(c, L.lanes, L.bytes, WAIT_MAIN, false)) return grc;
+    const pt::RaycastLayout M(mem.size);   // (the slab as allocated: a multiple of 64 lanes, at most a chunk's)
+    char* const m = mem.as<char>();
+    a.spill = (float2*)(m + M.spill);
+    static const bool timed = pt::knob_env("PT_RAYCAST_EVENTS") && pt::knob_int(pt::knob_env("PT_RAYCAST_EVENTS"), 0, 1);
+    static hipEvent_t ev[2] = {};
+    if (timed && !ev[0]) { HIPCHK(c, hipEventCreate(&ev[0])); HIPCHK(c, hipEventCreate(&ev[1])); }
+    float total_ms = 0.0f;
+    for (size_t i = 0; i < pt::RaycastLayout::chunks((size_t)n); i++) {
+        const size_t at = i * pt::kRaycastChunk, cn = pt::RaycastLayout::chunk_rays((size_t)n, i);
+        a.spill_stride = (unsigned)((cn + 63) & ~(size_t)63);   // the launch's lanes
+        const pt::RaycastArgs q{ (const float*)(m + M.origins), (const float*)(m + M.dirs), (float4*)(m + M.hits), (unsigned)cn };
+        HIPCHK(c, hipMemcpyAsync(m + M.origins, origins + 3 * at, cn * 12, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(m + M.dirs, dirs + 3 * at, cn * 12, hipMemcpyHostToDevice, c->stream));
+        if (timed) HIPCHK(c, hipEventRecord(ev[0], c->stream));
+        HIPCHK(c, pt_launch_raycast(fx->prog, &a, &q, c->stream));
+        if (timed) HIPCHK(c, hipEventRecord(ev[1], c->stream));
+        HIPCHK(c, hipMemcpyAsync(hits + at, m + M.hits, cn * sizeof(pt_ray_hit), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (timed) {
+            float ms = 0.0f;
+            HIPCHK(c, hipEventElapsedTime(&ms, ev[0], ev[1]));
+            total_ms += ms;
+        }
+    }
+    if (timed) g_raycast_ms = total_ms;
     return PT_OK;
 }
 

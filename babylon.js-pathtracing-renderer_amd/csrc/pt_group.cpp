@@ -860,6 +860,19 @@ int pt_denoise_variance(pt_ctx* c, const pt_texture* beauty, const pt_texture* n
                                            demodulate));
 }
 
+int pt_cast_rays(pt_effect* fx, const float* origins, const float* dirs, int n, pt_ray_hit* hits)
+{
+    if (!fx) return PT_ERR_ARG;
+    pt_ctx* c = fx->ctx;
+    if (!is_trace(fx->prog)) return fail(c, PT_ERR_ARG, "pt_cast_rays needs a path-tracing effect");
+    if (n < 0) return fail(c, PT_ERR_ARG, "pt_cast_rays: n must be >= 0");
+    if (n > 0 && (!origins || !dirs || !hits)) return fail(c, PT_ERR_ARG, "pt_cast_rays: NULL rays or records");
+    if (n == 0) return PT_OK;
+    // (every part holds the whole scene; forwarding to one of them is a follow-up)
+    if (c->n() > 1) return fail(c, PT_ERR_UNSUPPORTED, "pt_cast_rays needs a one-part context");
+    return take(c, 0, dev_cast_rays(fx->sub[0], origins, dirs, n, hits));
+}
+
 int pt_math_probe(pt_ctx* c, int op, const float* x, const float* y, float* out, int n)
 {
     if (!c) return PT_ERR_ARG;

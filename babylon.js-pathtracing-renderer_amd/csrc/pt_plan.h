@@ -1,7 +1,7 @@
 // pt_plan.h — the draw schedule's arithmetic (pt_capi.cpp issues the HIP calls it decides): which bands a
 // partition owns, how the carved slabs are laid out (a buffer set's compaction records, the child-pair build's
-// scratch and records, the wavefront buffers, the longest-first arrays, the spill slabs), which buffer set / side
-// stream / mark a megakernel draw takes, its grid, and the auto trial of late-bounce compaction. Plain host C++
+// scratch and records, the wavefront buffers, the longest-first arrays, the spill slabs, a ray query's slab), which
+// buffer set / side stream / mark a megakernel draw takes, its grid, and the auto trial of late-bounce compaction. Plain host C++
 // over plain numbers, no HIP and no allocation: tests/test_plan.py compiles it on its own and checks it by
 // hand-worked cases.
 #pragma once
@@ -158,6 +158,38 @@ struct LptLayout {
 constexpr size_t kSpillPerLane = kStackLevels - kStackLdsMin + 4;
 inline bool spill_fits(size_t lanes) { return lanes * kSpillPerLane <= 0xffffffffull; }
 inline size_t spill_slab(int p, size_t lanes) { return (size_t)p * lanes * kSpillPerLane; }
+
+// pt_cast_rays' slab (pt_raycast.hip), the call's own: frames in flight on the side streams use the spill slabs
+// above, which a query must not touch. One ray per lane of one-wave workgroups, so a launch of `rays` rays has
+// lanes = rays rounded up to 64. Byte offsets: origins, dirs [lanes x 12 B each] the staged rays | hits [lanes x
+// 64 B] the records | spill [(kStackLevels - kStackLdsMin) levels x lanes x 8 B] the stack levels beyond LDS,
+// [level][lane] with `lanes` the stride (no G-buffer fields: a query has none). A call of more than kRaycastChunk
+// rays runs as chunks of that many (the last one shorter) through the one slab: chunk i takes rays
+// [i * kRaycastChunk, ...). The chunk keeps the slab at 66 MB, far inside what the walks' 32-bit slab index
+// reaches (spill_fits).
+constexpr size_t kRaycastChunk = 262144;   // a multiple of 64
+constexpr size_t kRaycastLevels = kStackLevels - kStackLdsMin;
+struct RaycastLayout {
+    size_t lanes;
+    size_t origins, dirs, hits, spill, bytes;
+    explicit RaycastLayout(size_t rays)
+    {
+        const size_t r = rays < kRaycastChunk ? rays : kRaycastChunk;
+        lanes = (r + 63) & ~(size_t)63;
+        Carve c;
+        origins = c.take(lanes * 12); dirs = c.take(lanes * 12);
+        hits = c.take(lanes * 64);
+        spill = c.take(kRaycastLevels * lanes * 8);
+        bytes = c.at;
+    }
+    static size_t chunks(size_t rays) { return (rays + kRaycastChunk - 1) / kRaycastChunk; }
+    static size_t chunk_rays(size_t rays, size_t i)
+    {
+        const size_t done = i * kRaycastChunk;
+        return rays - done < kRaycastChunk ? rays - done : kRaycastChunk;
+    }
+};
+static_assert(kRaycastChunk % 64 == 0 && kRaycastChunk * kSpillPerLane <= 0xffffffffull, "a chunk's slab index fits 32 bits");
 
 // pt_canvas_encode_jpeg_sub's workspace (pt_jpeg_enc.hip) for a canvas of mcus_x x rows MCUs of 8 hs x 8 vs pixels
 // (Y sampled hs x vs: 1x1, 2x1 or 2x2), hs vs + 2 blocks each in coded order: the vs rows of hs Y blocks, Cb, Cr;

@@ -92,9 +92,11 @@ PT_D f3 sphereNormal(const TraceArgs& a, f3 rayO, f3 rayD, const Hit& h)
 // js/GLTFModelPathTracing_FragmentShader.js:116-346 (glTF, with the BVH walk)
 // SLIM (pt_trace and pt_cont of the 8-wave variants, kWaveBaseOf): fewer values live across the walk - `deep` is the
 // wave's base (MegaStack BASE), the sphere normal is formed after the walk (kNormalAfter)
+// `walked` (pt_raycast alone; the path kernels pass none, and inlined the copy is no code): the walk's result, for
+// the triangle and the barycentrics of a mesh hit
 template <int PROG, bool COUNT, int LS, bool SLIM>
 PT_D void sceneIntersect(const TraceArgs& a, f3 rayO, f3 rayD, Hit& h, float2* lds, unsigned lane_slot,
-                         unsigned deep, Cnt& cnt, bool firstHit)
+                         unsigned deep, Cnt& cnt, bool firstHit, BvhResult* walked = nullptr)
 {
     // `firstHit`: of this segment's hit only "the light / nothing / something else" is read (bounceStep
     // decides which segments). The walk may then stop at the first triangle closer than the analytic
@@ -148,6 +150,7 @@ PT_D void sceneIntersect(const TraceArgs& a, f3 rayO, f3 rayD, Hit& h, float2* l
     br.ws.flush(a.walk_stat, cnt.bounce++);
 #endif
     PT_SEC(cnt, 2);
+    if (walked) *walked = br;
     if (br.lookup && anyHit) {   // the mesh occludes: what shadeStep reads of a mesh hit, no lookup
         h.normal = mk(0.0f, 0.0f, 1.0f);
         h.type = a.uses_albedo ? PBR_MATERIAL : a.model_mat;

@@ -22,6 +22,7 @@
 //   effect.setFeatureTargets(normalRT, albedoRT)  -> pt_set_feature_targets (extension: accumulated G-buffer)
 //   engine.denoise(beautyRT, normalRT, albedoRT, dstRT, opts) -> pt_denoise (extension: a-trous filter over them)
 //   effect.setMomentTarget(momentsRT)             -> pt_set_moment_target (extension: accumulated luminance moments)
+//   effect.castRays(origins, dirs) / effect.pick(x, y) -> pt_cast_rays (extension: ray queries against the bound scene)
 //   engine.denoiseVariance(beautyRT, normalRT, albedoRT, momentsRT, dstRT, opts) -> pt_denoise_variance
 //   engine.encodeCanvasJPEG(quality, subsampling, optimize) -> pt_canvas_encode_jpeg_opt (extension: the canvas as a JPEG file)
 //   engine.encodeCanvasPNG(colour, filter) -> pt_canvas_encode_png (extension: the canvas as a PNG file, lossless)
@@ -477,9 +478,9 @@ function install(BABYLON, opts) {
   }
 
   class Effect {
-    constructor(ctx, handle) { this._ctx = ctx; this._pt = handle; }
+    constructor(ctx, handle) { this._ctx = ctx; this._pt = handle; this._cam = {}; }
     isReady() { return this._pt !== null; }
-    _f(name, arr) { if (this._pt) check(this._ctx, addon.pt_set_float(this._pt, name, arr), 'set ' + name); return this; }
+    _f(name, arr) { if (CAMERA_UNIFORMS.has(name)) this._cam[name] = Float32Array.from(arr); if (this._pt) check(this._ctx, addon.pt_set_float(this._pt, name, arr), 'set ' + name); return this; }
     setFloat(n, v) { return this._f(n, [v]); }
     setFloat2(n, a, b) { return this._f(n, [a, b]); }
     setFloat3(n, a, b, c) { return this._f(n, [a, b, c]); }
@@ -515,6 +516,35 @@ function install(BABYLON, opts) {
     setMomentTarget(momentsRT) {
       if (this._pt) check(this._ctx, addon.pt_set_moment_target(this._pt, momentsRT ? momentsRT._pt : null), 'setMomentTarget');
       return this;
+    }
+    // MI355X extension (pt_cast_rays): SceneIntersect of this path-tracing effect's program, with the uniforms and
+    // data textures bound now, on world-space rays (3 floats per ray each). Returns an ArrayBuffer of 64-byte records
+    // (include/pt.h pt_ray_hit: t, object_id, type, triangle | normal.xyz, bary_u | color.xyz, bary_v | uv.xy, 0, 0),
+    // or null when the call fails (reported through onError)
+    castRays(origins, dirs) {
+      if (!this._pt) return null;
+      const r = addon.pt_cast_rays(this._pt, origins, dirs);
+      if (typeof r === 'number') { check(this._ctx, r, 'castRays'); return null; }
+      return r;
+    }
+    // ... the pinhole ray through the centre of pixel (x, y) (row 0 the bottom one, as gl_FragCoord; width x height
+    // default to uResolution), formed in float32 from uCameraMatrix, uULen and uVLen as the shaders' main() forms its
+    // direction - no jitter, no aperture - then normalised: { t, objectId, type, triangle, normal, baryU, baryV,
+    // color, uv, hit }, t a valid uFocusDistance when `hit`
+    pick(x, y, width, height) {
+      const f = Math.fround, c = this._cam;
+      const m = c.uCameraMatrix || new Float32Array(16);
+      const ulen = c.uULen ? c.uULen[0] : 0, vlen = c.uVLen ? c.uVLen[0] : 0;
+      const w = width !== undefined ? width : (c.uResolution ? c.uResolution[0] : 0);
+      const h = height !== undefined ? height : (c.uResolution ? c.uResolution[1] : 0);
+      const ppx = f(f(f(f(x) + 0.5) / f(w)) * 2 - 1), ppy = f(f(f(f(y) + 0.5) / f(h)) * 2 - 1);
+      const d = [0, 1, 2].map((k) => f(f(f(f(m[k] * ppx) * ulen) + f(f(m[4 + k] * ppy) * vlen)) + m[8 + k]));
+      const inv = f(1 / f(Math.sqrt(f(f(f(d[0] * d[0]) + f(d[1] * d[1])) + f(d[2] * d[2])))));
+      const buf = this.castRays(new Float32Array([m[12], m[13], m[14]]), new Float32Array(d.map((v) => f(v * inv))));
+      if (!buf) return null;
+      const F = new Float32Array(buf), I = new Int32Array(buf);
+      return { t: F[0], objectId: I[1], type: I[2], triangle: I[3], normal: [F[4], F[5], F[6]], baryU: F[7],
+        color: [F[8], F[9], F[10]], baryV: F[11], uv: [F[12], F[13]], hit: I[1] >= 0 };
     }
   }
 
@@ -571,5 +601,8 @@ function nativeBVH(addon, device) {
     aabbArray.set(out, 0);
   };
 }
+
+// the float uniforms Effect.pick forms its ray from (the shim keeps their last values)
+const CAMERA_UNIFORMS = new Set(['uCameraMatrix', 'uULen', 'uVLen', 'uResolution']);
 
 module.exports = { install, decodePNG, decodeHDR, decodeImage, nativeBVH, loadAddon };

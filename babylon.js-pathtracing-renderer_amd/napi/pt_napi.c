@@ -597,6 +597,22 @@ static napi_value DenoiseVariance(napi_env env, napi_callback_info info)
                                         (const pt_texture*)handle(env, a[4]), (pt_texture*)handle(env, a[5]),
                                         i32(env, a[6]), (float)f64(env, a[7]), (float)f64(env, a[8]), i32(env, a[9])));
 }
+/* pt_cast_rays(effect, origins: Float32Array (3 per ray), dirs: Float32Array (3 per ray)) -> ArrayBuffer of
+ * pt_ray_hit records (64 B per ray), or the status when the call fails */
+static napi_value CastRays(napi_env env, napi_callback_info info)
+{
+    napi_value a[MAXARGS]; if (args(env, info, a, 3) < 0) return NULL;
+    size_t lo, ld;
+    const float* org = (const float*)bytes_of(env, a[1], &lo);
+    const float* dir = (const float*)bytes_of(env, a[2], &ld);
+    if (lo != ld || lo % 12 != 0 || lo / 12 > 0x7fffffffu) return num(env, PT_ERR_ARG);
+    const int n = (int)(lo / 12);
+    void* hits = NULL;
+    napi_value ab;
+    CHECK(napi_create_arraybuffer(env, (size_t)n * sizeof(pt_ray_hit), &hits, &ab));
+    const int rc = pt_cast_rays((pt_effect*)handle(env, a[0]), org, dir, n, (pt_ray_hit*)hits);
+    return rc == PT_OK ? ab : num(env, rc);
+}
 /* pt_bvh_build(aabbIn: Float32Array (9 per triangle), work: Uint32Array, out: Float32Array) -> node count */
 static napi_value BvhBuild(napi_env env, napi_callback_info info)
 {
@@ -683,6 +699,7 @@ static napi_value Init(napi_env env, napi_value exports)
         { "pt_set_counting", SetCounting }, { "pt_read_counters", ReadCounters }, { "pt_reset_counters", ResetCounters }, { "pt_queue_stats", QueueStats }, { "pt_cont_stats", ContStats }, { "pt_fuse_stats", FuseStats },
         { "pt_set_feature_targets", SetFeatureTargets }, { "pt_denoise", Denoise },
         { "pt_set_moment_target", SetMomentTarget }, { "pt_denoise_variance", DenoiseVariance },
+        { "pt_cast_rays", CastRays },
         { "pt_bvh_build", BvhBuild }, { "pt_bvh_build_gpu", BvhBuildGpu },
         { "pt_jpeg_size", JpegSize }, { "pt_jpeg_decode_rgba8", JpegDecode }, { "pt_version", Version },
     };

@@ -42,7 +42,7 @@ SYMBOLS = [
     "pt_canvas_encode_png", "pt_target_encode_hdr", "pt_targets_encode_exr", "pt_targets_encode_exr_begin", "pt_canvas_encode_jpeg_begin", "pt_canvas_encode_png_begin", "pt_target_encode_hdr_begin", "pt_canvas_read_begin", "pt_job_poll", "pt_job_finish", "pt_job_cancel", "pt_job_stats",
     "pt_write_pixels",
     "pt_set_row_partition", "pt_set_output_partition", "pt_canvas_wrap", "pt_set_backend", "pt_set_bvh_layout", "pt_bvh_layout_used", "pt_set_stream", "pt_texture_device_ptr", "pt_last_render_ms", "pt_timing_begin", "pt_timing_end", "pt_timing_latency",
-    "pt_set_counting", "pt_read_counters", "pt_reset_counters", "pt_queue_stats", "pt_cont_stats", "pt_fuse_stats", "pt_set_feature_targets", "pt_denoise", "pt_set_moment_target", "pt_denoise_variance", "pt_math_probe", "pt_math_exhaustive", "pt_bvh_build", "pt_bvh_build_gpu", "pt_jpeg_size", "pt_jpeg_decode_rgba8", "pt_version",
+    "pt_set_counting", "pt_read_counters", "pt_reset_counters", "pt_queue_stats", "pt_cont_stats", "pt_fuse_stats", "pt_set_feature_targets", "pt_denoise", "pt_set_moment_target", "pt_denoise_variance", "pt_cast_rays", "pt_math_probe", "pt_math_exhaustive", "pt_bvh_build", "pt_bvh_build_gpu", "pt_jpeg_size", "pt_jpeg_decode_rgba8", "pt_version",
 ]
 
 
@@ -54,6 +54,13 @@ class ExrChannel(ctypes.Structure):
 
 
 _lib = None
+
+
+# pt_ray_hit (include/pt.h): one 64-byte record per ray of Effect.cast_rays
+RAY_HIT = np.dtype([("t", "<f4"), ("object_id", "<i4"), ("type", "<i4"), ("triangle", "<i4"), ("normal", "<f4", (3,)),
+                    ("bary_u", "<f4"), ("color", "<f4", (3,)), ("bary_v", "<f4"), ("uv", "<f4", (2,)),
+                    ("reserved", "<f4", (2,))])
+RAY_MISS_T = np.float32(1000000.0)   # the shaders' INFINITY
 
 
 def lib():
@@ -119,6 +126,7 @@ def lib():
         "pt_denoise": ([vp, vp, vp, vp, vp, i32, ctypes.c_float, ctypes.c_float, i32], i32),
         "pt_set_moment_target": ([vp, vp], i32),
         "pt_denoise_variance": ([vp, vp, vp, vp, vp, vp, i32, ctypes.c_float, ctypes.c_float, i32], i32),
+        "pt_cast_rays": ([vp, vp, vp, i32, vp], i32),
         "pt_queue_stats": ([vp, ctypes.POINTER(ctypes.c_uint32)], i32), "pt_version": ([], ctypes.c_char_p),
     }
     for name, (args, res) in sig.items():
@@ -707,6 +715,54 @@ class Effect:
         history rule - moments = (sum of L, sum of L^2, 0, weight). None unbinds it."""
         self.engine.check(lib().pt_set_moment_target(self.handle, moments.handle if moments is not None else None),
                           "setMomentTarget")
+
+
+    def cast_rays(self, origins, dirs):
+        """MI355X extension (pt_cast_rays): SceneIntersect of this path-tracing effect's program, with the uniforms
+        and data textures bound now, on world-space rays. `origins` and `dirs` are (n, 3) float32; returns n RAY_HIT
+        records (t in units of |dir|; on a miss t = RAY_MISS_T, object_id -1, type -100, triangle -1, the rest 0)."""
+        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        if o.shape != d.shape:
+            raise ValueError("cast_rays: origins and dirs must both be (n, 3)")
+        hits = np.zeros(o.shape[0], RAY_HIT)
+        self.engine.check(lib().pt_cast_rays(self.handle, o.ctypes.data if len(o) else None, d.ctypes.data if len(d) else None,
+                                             o.shape[0], hits.ctypes.data if len(o) else None), "pt_cast_rays")
+        return hits
+
+    def _uniform(self, name, n):
+        """The last value this effect's float uniform `name` was given, as n float32 (GLSL's zeros while unset)."""
+        bits = self._cache.get(name)
+        out = np.zeros(n, np.float32)
+        if isinstance(bits, bytes):
+            v = np.frombuffer(bits, np.float32)
+            out[:min(n, len(v))] = v[:n]
+        return out
+
+    def camera_ray(self, x, y, width, height):
+        """The pinhole ray through the centre of pixel (x, y) of a width x height target (row 0 the bottom one, as
+        gl_FragCoord), formed in float32 from uCameraMatrix, uULen and uVLen the way the shaders' main() forms its
+        direction - no jitter, no aperture - then normalised: (origin, direction), float32 (3,) each."""
+        f = np.float32
+        m = self._uniform("uCameraMatrix", 16)
+        ulen, vlen = self._uniform("uULen", 1)[0], self._uniform("uVLen", 1)[0]
+        ppx = ((f(x) + f(0.5)) / f(width)) * f(2.0) - f(1.0)
+        ppy = ((f(y) + f(0.5)) / f(height)) * f(2.0) - f(1.0)
+        with np.errstate(all="ignore"):
+            d = (m[0:3] * ppx) * ulen + (m[4:7] * ppy) * vlen + m[8:11]
+            inv = f(1.0) / np.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2])
+            d = d * inv
+        return m[12:15].copy(), d.astype(np.float32)
+
+    def pick(self, x, y, width, height):
+        """The RAY_HIT record of camera_ray(x, y, width, height): what lies under that pixel."""
+        o, d = self.camera_ray(x, y, width, height)
+        return self.cast_rays(o[None, :], d[None, :])[0]
+
+    def autofocus(self, x, y, width, height):
+        """The distance to what lies under pixel (x, y) - a valid uFocusDistance - or None when the ray misses."""
+        h = self.pick(x, y, width, height)
+        return None if h["object_id"] < 0 else float(h["t"])
 
 
 class EffectWrapper:

@@ -548,6 +548,39 @@ int pt_set_moment_target(pt_effect* fx, pt_texture* moments);
 int pt_denoise_variance(pt_ctx* ctx, const pt_texture* beauty, const pt_texture* normal_id,
                         const pt_texture* albedo_weight, const pt_texture* moments, pt_texture* dst,
                         int iterations, float sigma_normal, float sigma_luminance, int demodulate);
+/* Ray queries: SceneIntersect of a path-tracing effect's program on caller-given rays. For each of `n` world-space
+ * rays (origins[3i..3i+2], dirs[3i..3i+2]) hits[i] holds exactly what the effect's program computes in
+ * SceneIntersect for that ray: the uniforms and data textures are the ones bound now (SetupScene, the model
+ * matrix, the material switches, the BVH and triangle textures), the walk is the one pt_set_bvh_layout selects, the
+ * query is the closest hit, and nothing of CalculateRadiance is computed. It needs no render target, previousBuffer
+ * or blue noise, and no draw before it. The direction is taken as given: t is in units of its length (for a
+ * normalised direction t is a distance, and a valid uFocusDistance for a camera ray). A component that is zero,
+ * negative zero, infinite or NaN is an input like any other: the record is what the arithmetic gives. On a miss
+ * t is the shaders' INFINITY constant (1000000.0), object_id -1, type -100, triangle -1 and every other field +0.0.
+ * Synchronous: the call is queued on the context's stream after everything queued so far (so a pt_write_pixels
+ * into a BVH texture before it is seen) and returns with `hits` filled. It observes no render target, so a deferred
+ * screenCopy stays deferred; it writes no texture, counter, statistic, cost table, tile order or timing window, and
+ * the walk's stack levels beyond LDS go to a slab of the call's own, never the draws': a draw after it gives the bits
+ * it gives without it, with several frames in flight too. Rays and records pass through context-owned device
+ * staging that grows on demand; a large call runs in chunks inside the one call. A mesh deeper than the shaders'
+ * stackLevels[28] is reported as for a draw: by the next pt_sync, as PT_ERR_DATA.
+ * PT_ERR_ARG, before any device work: a bad handle, a screenCopy / screenOutput effect, n < 0, a NULL pointer with
+ * n > 0. n == 0 is PT_OK and touches nothing. PT_ERR_UNSUPPORTED: a context of several parts, as pt_denoise.
+ * PT_ERR_STATE: a mesh program without tAABBTexture / tTriangleTexture bound as RGBA32F data textures. */
+typedef struct pt_ray_hit {          /* 64 bytes, one line per ray */
+    float   t;                       /* SceneIntersect's hitT; INFINITY (1000000.0) on a miss */
+    int32_t object_id;               /* hitObjectID; -1 on a miss */
+    int32_t type;                    /* hitType (the shaders' material constants); -100 on a miss */
+    int32_t triangle;                /* mesh hit: the triangle's index in tTriangleTexture (8 texels each); else -1 */
+    float   normal[3];               /* hitNormal, world space, as SceneIntersect leaves it (not normalised again; the
+                                        bump map applied where the program applies it) */
+    float   bary_u;                  /* mesh hit: the walk's triU; else 0 */
+    float   color[3];                /* hitColor as SceneIntersect writes it (1,1,1 for the mesh) */
+    float   bary_v;                  /* mesh hit: the walk's triV; else 0 */
+    float   uv[2];                   /* mesh hit: the interpolated hit uv; else 0 */
+    float   reserved[2];             /* +0.0 */
+} pt_ray_hit;
+int pt_cast_rays(pt_effect* fx, const float* origins, const float* dirs, int n, pt_ray_hit* hits);
 /* Device self-test of the pinned GLSL built-ins (ops as the oracle's pto_math_probe). */
 int pt_math_probe(pt_ctx* ctx, int op, const float* x, const float* y, float* out, int n);
 /* Exhaustive device self-test of a fast built-in sequence against the IEEE operation it replaces,
