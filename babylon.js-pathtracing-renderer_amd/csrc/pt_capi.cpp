@@ -26,8 +26,9 @@
 //                      pending before anything else could observe it).
 // dev_denoise (pt_denoise) is no draw: the à-trous filter's prep and passes (pt_denoise.hip) on the main stream.
 // dev_denoise_variance (pt_denoise_variance) likewise (pt_denoise_var.hip), with a slab of its own.
-// dev_cast_rays (pt_cast_rays) is no draw either: SceneIntersect of an effect's scene on the caller's rays (pt_raycast.hip),
-// synchronous on the main stream, with a slab of its own and no trace in any target, counter or statistic.
+// dev_cast_rays_ex (pt_cast_rays, pt_cast_rays_ex) is no draw either: SceneIntersect of an effect's scene on the caller's
+// rays (pt_raycast.hip), on the main stream - synchronous for host rays, enqueued for device rays - with slabs of its
+// own and no trace in any target, counter or statistic.
 // The main stream is the context's own or the caller's (dev_set_stream); per-draw timing events are off
 // until asked for (pt_last_render_ms, the timing window).
 #include "../../include/pt.h"
@@ -198,8 +199,10 @@ struct Dev {
     // it assembles (bytes). HDR pt_target_encode_hdr's workspace (bytes; pt::HdrLayout) and HDR_OUT the coded scanlines
     // (bytes: the target's bound, so the encode needs no length from the host). EXR pt_targets_encode_exr's workspace
     // (bytes; pt::ExrLayout) and EXR_OUT its offset table and chunks (bytes: the bound, likewise). RAYCAST pt_cast_rays'
-    // staged rays, records and stack slab (lanes; pt::RaycastLayout).
-    enum Slab { WF, LPT, SPILL, RAD, FEAT, CONT, GB, DENOISE, DENOISE_VAR, JPEG, JPEG_OUT, JPEG_OPT, PNG, PNG_OUT, HDR, HDR_OUT, EXR, EXR_OUT, RAYCAST, kSlabs };
+    // staged rays, records and stack slab (lanes; pt::RaycastLayout), RAYCAST_BOUND the staged bounds and flags of
+    // pt_cast_rays_ex's host route (lanes; pt::RaycastBoundLayout) and RAYCAST_STACK its device route's stack slab
+    // (lanes; pt::RaycastStackLayout).
+    enum Slab { WF, LPT, SPILL, RAD, FEAT, CONT, GB, DENOISE, DENOISE_VAR, JPEG, JPEG_OUT, JPEG_OPT, PNG, PNG_OUT, HDR, HDR_OUT, EXR, EXR_OUT, RAYCAST, RAYCAST_BOUND, RAYCAST_STACK, kSlabs };
     DevMem slab[kSlabs];
     pt::WfBufs wf = {};
     size_t wf_pixels = 0, wf_spill = 0;
@@ -1297,12 +1300,15 @@ void dev_ctx_destroy(Dev* c)
 
 const char* dev_last_error(Dev* c) { return c ? c->err.c_str() : "no context"; }
 
+static void raycast_events_read();
+
 int dev_sync(Dev* c)
 {
     if (!c) return PT_ERR_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = flush_deferred(c)) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    raycast_events_read();   // (a device ray query's events under PT_RAYCAST_EVENTS; nothing otherwise)
     unsigned flags = 0;
     HIPCHK(c, hipMemcpy(&flags, c->d_err, sizeof(flags), hipMemcpyDeviceToHost));
     if (flags) {   // (on the main stream, which the next draw's path tracing waits for: not the null stream)
@@ -2515,22 +2521,49 @@ int dev_math_exhaustive(Dev* c, int op, uint64_t* mismatches)
     return PT_OK;
 }
 
-// pt_cast_rays: checked by the caller (pt_group.cpp) but for the scene, which scene_args checks; then, chunk by chunk
-// (pt::RaycastLayout), the rays staged into the call's slab, pt_raycast, and the records copied back, all on the main
-// stream - behind every draw's path tracing, which the main stream already waits for (draw_mega), so the slab of a
-// query is never a frame's, and a BVH texture written before the call is seen. It observes no render target: what
-// is deferred stays deferred. No timing events, no counters; scene_args' note of the walk the last draw took
-// (pt_bvh_layout_used) is put back.
+// pt_cast_rays and pt_cast_rays_ex: checked by the caller (pt_group.cpp) but for the scene, which scene_args checks;
+// then, chunk by chunk (pt::RaycastLayout), on the main stream - behind every draw's path tracing, which the main
+// stream already waits for (draw_mega), so the slab of a query is never a frame's, and a BVH texture written before
+// the call is seen. It observes no render target: what is deferred stays deferred. No timing events, no counters;
+// scene_args' note of the walk the last draw took (pt_bvh_layout_used) is put back.
+//  * PT_RAYS_HOST: a chunk's rays (and bounds) staged into the call's slabs, the kernel, the records or flags copied
+//    back, a synchronise. The unbounded closest hit - pt_cast_rays - is pt_raycast as before; a bound or the
+//    occlusion mode takes pt_raycast_q, and stages t_max / the flags in slab[RAYCAST_BOUND] (pt::RaycastBoundLayout).
+//  * PT_RAYS_DEVICE: nothing staged and nothing awaited - one launch per chunk on the caller's arrays at the chunk's
+//    offset, with slab[RAYCAST_STACK] (pt::RaycastStackLayout: the stack levels alone) shared by the chunks, which the
+//    stream runs one after the other. Growing that slab waits for the main stream, so for the calls still in flight.
 // Measurement (tools/raycast_rate.py): with PT_RAYCAST_EVENTS=1 in the environment the kernel launches of a call are
 // bracketed by events, and pt_debug_raycast_ms returns the last call's kernel time (-1: none); unset, no event is
-// recorded.
+// recorded. A device call does not wait for its events: they are read by the next query, by pt_sync, or by
+// pt_debug_raycast_ms itself, whichever comes first.
 static float g_raycast_ms = -1.0f;
-extern "C" __attribute__((visibility("default"))) float pt_debug_raycast_ms(void) { return g_raycast_ms; }
-
-int dev_cast_rays(DevFx* fx, const float* origins, const float* dirs, int n, pt_ray_hit* hits)
+static std::vector<std::pair<hipEvent_t, hipEvent_t>> g_raycast_pending;   // a device call's launches, not yet read
+static void raycast_events_read()
 {
-    if (!fx || n < 0 || (n > 0 && (!origins || !dirs || !hits))) return PT_ERR_ARG;
-    if (n == 0) return PT_OK;
+    if (g_raycast_pending.empty()) return;
+    float total_ms = 0.0f;
+    for (auto& e : g_raycast_pending) {
+        float ms = 0.0f;
+        if (hipEventSynchronize(e.second) == hipSuccess && hipEventElapsedTime(&ms, e.first, e.second) == hipSuccess) total_ms += ms;
+        (void)hipEventDestroy(e.first);
+        (void)hipEventDestroy(e.second);
+    }
+    g_raycast_pending.clear();
+    g_raycast_ms = total_ms;
+}
+extern "C" __attribute__((visibility("default"))) float pt_debug_raycast_ms(void)
+{
+    raycast_events_read();
+    return g_raycast_ms;
+}
+
+int dev_cast_rays_ex(DevFx* fx, const pt_ray_query* rq)
+{
+    if (!fx || !rq || rq->n < 0 || (rq->n > 0 && (!rq->origins || !rq->dirs || !rq->out))) return PT_ERR_ARG;
+    if (rq->n == 0) return PT_OK;
+    const size_t n = (size_t)rq->n;
+    const bool occluded = rq->mode == PT_RAYS_OCCLUDED, device = rq->memory == PT_RAYS_DEVICE;
+    const bool plain = !occluded && !rq->t_max;   // pt_cast_rays' query: pt_raycast itself
     Dev* c = fx->ctx;
     HIPCHK(c, hipSetDevice(c->device));
     pt::TraceArgs a;
@@ -2540,27 +2573,64 @@ int dev_cast_rays(DevFx* fx, const float* origins, const float* dirs, int n, pt_
     const int rc = scene_args(fx, a, mesh);
     c->bvh_used = used;
     if (rc) return rc;
-    const pt::RaycastLayout L((size_t)n);
+    static const bool timed = pt::knob_env("PT_RAYCAST_EVENTS") && pt::knob_int(pt::knob_env("PT_RAYCAST_EVENTS"), 0, 1);
+    if (timed) raycast_events_read();
+    auto launch = [&](const pt::RaycastArgs& q) {
+        return plain ? pt_launch_raycast(fx->prog, &a, &q, c->stream)
+                     : pt_launch_raycast_q(fx->prog, occluded ? pt::RAYS_OCCLUDED : pt::RAYS_CLOSEST, &a, &q, c->stream);
+    };
+    if (device) {
+        const pt::RaycastStackLayout L(n);
+        DevMem& mem = c->slab[Dev::RAYCAST_STACK];
+        if (L.lanes > mem.size)
+            if (int grc = mem.grow(c, L.lanes, L.bytes, WAIT_MAIN, false)) return grc;
+        a.spill = (float2*)(mem.as<char>() + pt::RaycastStackLayout(mem.size).spill);
+        for (size_t i = 0; i < pt::RaycastLayout::chunks(n); i++) {
+            const size_t at = i * pt::kRaycastChunk, cn = pt::RaycastLayout::chunk_rays(n, i);
+            a.spill_stride = (unsigned)((cn + 63) & ~(size_t)63);   // the launch's lanes
+            const pt::RaycastArgs q{ rq->origins + 3 * at, rq->dirs + 3 * at, occluded ? nullptr : (float4*)rq->out + 4 * at,
+                                     (unsigned)cn, rq->t_max ? rq->t_max + at : nullptr,
+                                     occluded ? (unsigned char*)rq->out + at : nullptr };
+            hipEvent_t ev[2] = {};
+            if (timed) { HIPCHK(c, hipEventCreate(&ev[0])); HIPCHK(c, hipEventCreate(&ev[1])); HIPCHK(c, hipEventRecord(ev[0], c->stream)); }
+            HIPCHK(c, launch(q));
+            if (timed) { HIPCHK(c, hipEventRecord(ev[1], c->stream)); g_raycast_pending.emplace_back(ev[0], ev[1]); }
+        }
+        return PT_OK;
+    }
+    const pt::RaycastLayout L(n);
     DevMem& mem = c->slab[Dev::RAYCAST];
     if (L.lanes > mem.size)
         if (int grc = mem.grow(c, L.lanes, L.bytes, WAIT_MAIN, false)) return grc;
     const pt::RaycastLayout M(mem.size);   // (the slab as allocated: a multiple of 64 lanes, at most a chunk's)
     char* const m = mem.as<char>();
     a.spill = (float2*)(m + M.spill);
-    static const bool timed = pt::knob_env("PT_RAYCAST_EVENTS") && pt::knob_int(pt::knob_env("PT_RAYCAST_EVENTS"), 0, 1);
+    char* b = nullptr;                     // the bounds going in and the flags coming out, staged beside it
+    size_t b_tmax = 0, b_flags = 0;
+    if (!plain) {
+        const pt::RaycastBoundLayout BL(n);
+        DevMem& bm = c->slab[Dev::RAYCAST_BOUND];
+        if (BL.lanes > bm.size)
+            if (int grc = bm.grow(c, BL.lanes, BL.bytes, WAIT_MAIN, false)) return grc;
+        const pt::RaycastBoundLayout BM(bm.size);
+        b = bm.as<char>(); b_tmax = BM.t_max; b_flags = BM.flags;
+    }
     static hipEvent_t ev[2] = {};
     if (timed && !ev[0]) { HIPCHK(c, hipEventCreate(&ev[0])); HIPCHK(c, hipEventCreate(&ev[1])); }
     float total_ms = 0.0f;
-    for (size_t i = 0; i < pt::RaycastLayout::chunks((size_t)n); i++) {
-        const size_t at = i * pt::kRaycastChunk, cn = pt::RaycastLayout::chunk_rays((size_t)n, i);
+    for (size_t i = 0; i < pt::RaycastLayout::chunks(n); i++) {
+        const size_t at = i * pt::kRaycastChunk, cn = pt::RaycastLayout::chunk_rays(n, i);
         a.spill_stride = (unsigned)((cn + 63) & ~(size_t)63);   // the launch's lanes
-        const pt::RaycastArgs q{ (const float*)(m + M.origins), (const float*)(m + M.dirs), (float4*)(m + M.hits), (unsigned)cn };
-        HIPCHK(c, hipMemcpyAsync(m + M.origins, origins + 3 * at, cn * 12, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(m + M.dirs, dirs + 3 * at, cn * 12, hipMemcpyHostToDevice, c->stream));
+        const pt::RaycastArgs q{ (const float*)(m + M.origins), (const float*)(m + M.dirs), (float4*)(m + M.hits), (unsigned)cn,
+                                 rq->t_max ? (const float*)(b + b_tmax) : nullptr, occluded ? (unsigned char*)(b + b_flags) : nullptr };
+        HIPCHK(c, hipMemcpyAsync(m + M.origins, rq->origins + 3 * at, cn * 12, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(m + M.dirs, rq->dirs + 3 * at, cn * 12, hipMemcpyHostToDevice, c->stream));
+        if (rq->t_max) HIPCHK(c, hipMemcpyAsync(b + b_tmax, rq->t_max + at, cn * 4, hipMemcpyHostToDevice, c->stream));
         if (timed) HIPCHK(c, hipEventRecord(ev[0], c->stream));
-        HIPCHK(c, pt_launch_raycast(fx->prog, &a, &q, c->stream));
+        HIPCHK(c, launch(q));
         if (timed) HIPCHK(c, hipEventRecord(ev[1], c->stream));
-        HIPCHK(c, hipMemcpyAsync(hits + at, m + M.hits, cn * sizeof(pt_ray_hit), hipMemcpyDeviceToHost, c->stream));
+        if (occluded) HIPCHK(c, hipMemcpyAsync((unsigned char*)rq->out + at, b + b_flags, cn, hipMemcpyDeviceToHost, c->stream));
+        else HIPCHK(c, hipMemcpyAsync((pt_ray_hit*)rq->out + at, m + M.hits, cn * sizeof(pt_ray_hit), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (timed) {
             float ms = 0.0f;
@@ -2570,6 +2640,12 @@ int dev_cast_rays(DevFx* fx, const float* origins, const float* dirs, int n, pt_
     }
     if (timed) g_raycast_ms = total_ms;
     return PT_OK;
+}
+
+int dev_cast_rays(DevFx* fx, const float* origins, const float* dirs, int n, pt_ray_hit* hits)
+{
+    const pt_ray_query q{ origins, dirs, nullptr, hits, n, PT_RAYS_CLOSEST, PT_RAYS_HOST };
+    return dev_cast_rays_ex(fx, &q);
 }
 
 int dev_math_probe(Dev* c, int op, const float* x, const float* y, float* out, int n)

@@ -99,6 +99,7 @@ Dev* dev_job_dev(pt_job* job);
 void dev_set_owner(Dev* c, void* owner);   // the context a part belongs to, for the calls that get a job alone
 void* dev_owner(Dev* c);
 int dev_cast_rays(DevFx* fx, const float* origins, const float* dirs, int n, pt_ray_hit* hits);
+int dev_cast_rays_ex(DevFx* fx, const pt_ray_query* q);
 int dev_math_exhaustive(Dev* c, int op, uint64_t* mismatches);
 int dev_math_probe(Dev* c, int op, const float* x, const float* y, float* out, int n);
 

@@ -873,6 +873,27 @@ int pt_cast_rays(pt_effect* fx, const float* origins, const float* dirs, int n, 
     return take(c, 0, dev_cast_rays(fx->sub[0], origins, dirs, n, hits));
 }
 
+int pt_cast_rays_ex(pt_effect* fx, const pt_ray_query* q)
+{
+    if (!fx) return PT_ERR_ARG;
+    pt_ctx* c = fx->ctx;
+    if (!q) return fail(c, PT_ERR_ARG, "pt_cast_rays_ex: NULL query");
+    if (!is_trace(fx->prog)) return fail(c, PT_ERR_ARG, "pt_cast_rays_ex needs a path-tracing effect");
+    if (q->mode != PT_RAYS_CLOSEST && q->mode != PT_RAYS_OCCLUDED) return fail(c, PT_ERR_ARG, "pt_cast_rays_ex: unknown mode");
+    if (q->memory != PT_RAYS_HOST && q->memory != PT_RAYS_DEVICE) return fail(c, PT_ERR_ARG, "pt_cast_rays_ex: unknown memory");
+    if (q->n < 0) return fail(c, PT_ERR_ARG, "pt_cast_rays_ex: n must be >= 0");
+    if (q->n > 0 && (!q->origins || !q->dirs || !q->out)) return fail(c, PT_ERR_ARG, "pt_cast_rays_ex: NULL rays or output");
+    if (q->n == 0) return PT_OK;
+    if (q->memory == PT_RAYS_DEVICE) {
+        const uintptr_t f = (uintptr_t)q->origins | (uintptr_t)q->dirs | (uintptr_t)q->t_max;
+        if (f & 3u) return fail(c, PT_ERR_ARG, "pt_cast_rays_ex: device rays and bounds must be 4-byte aligned");
+        if (q->mode == PT_RAYS_CLOSEST && ((uintptr_t)q->out & 15u))
+            return fail(c, PT_ERR_ARG, "pt_cast_rays_ex: device records must be 16-byte aligned");
+    }
+    if (c->n() > 1) return fail(c, PT_ERR_UNSUPPORTED, "pt_cast_rays_ex needs a one-part context");
+    return take(c, 0, dev_cast_rays_ex(fx->sub[0], q));
+}
+
 int pt_math_probe(pt_ctx* c, int op, const float* x, const float* y, float* out, int n)
 {
     if (!c) return PT_ERR_ARG;

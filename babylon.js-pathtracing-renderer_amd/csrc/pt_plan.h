@@ -190,6 +190,34 @@ struct RaycastLayout {
     }
 };
 static_assert(kRaycastChunk % 64 == 0 && kRaycastChunk * kSpillPerLane <= 0xffffffffull, "a chunk's slab index fits 32 bits");
+// pt_cast_rays_ex's siblings of it, slabs of their own with the same lanes and chunks. RaycastBoundLayout: what the
+// host route stages beside RaycastLayout's rays and records - t_max [lanes x 4 B] the bounds going in | flags
+// [lanes x 1 B] the occlusion query's bytes coming out. RaycastStackLayout: the device route's slab, with no ray or
+// record region (the kernel reads the caller's rays and writes the caller's output): spill alone, [(kStackLevels -
+// kStackLdsMin) levels x lanes x 8 B], 46 MB at a full chunk.
+struct RaycastBoundLayout {
+    size_t lanes;
+    size_t t_max, flags, bytes;
+    explicit RaycastBoundLayout(size_t rays)
+    {
+        lanes = RaycastLayout(rays).lanes;
+        Carve c;
+        t_max = c.take(lanes * 4);
+        flags = c.take(lanes);
+        bytes = c.at;
+    }
+};
+struct RaycastStackLayout {
+    size_t lanes;
+    size_t spill, bytes;
+    explicit RaycastStackLayout(size_t rays)
+    {
+        lanes = RaycastLayout(rays).lanes;
+        Carve c;
+        spill = c.take(kRaycastLevels * lanes * 8);
+        bytes = c.at;
+    }
+};
 
 // pt_canvas_encode_jpeg_sub's workspace (pt_jpeg_enc.hip) for a canvas of mcus_x x rows MCUs of 8 hs x 8 vs pixels
 // (Y sampled hs x vs: 1x1, 2x1 or 2x2), hs vs + 2 blocks each in coded order: the vs rows of hs Y blocks, Cb, Cr;

@@ -269,11 +269,14 @@ PT_D void objectMaterial(const TraceArgs& a, int id, f3& color, int& type)
 // last write survives). The object loops stay rolled (#pragma unroll 1): each iteration re-reads
 // its object from the kernarg segment through the scalar cache, which keeps ~130 wave-uniform
 // floats out of VGPRs and the code small enough for the instruction cache.
+// `start`: where hitT starts. The GLSL's is INFINITY, and the path kernels pass none; a bounded ray query
+// (pt_raycast.hip) starts it lower, and every `d < hitT` below then holds for it as it is: an object not nearer
+// than the bound is not taken, and h.id stays -1 with h.t the bound when none is.
 template <int PROG>
-PT_D void analyticNearest(const TraceArgs& a, f3 rayO, f3 rayD, Hit& h, f3& sn)
+PT_D void analyticNearest(const TraceArgs& a, f3 rayO, f3 rayD, Hit& h, f3& sn, float start = kINF)
 {
     constexpr int q0 = kQuadId0<PROG>;
-    h.t = kINF;
+    h.t = start;
     h.type = -100;
     h.id = -1;
     sn = mk(0, 0, 0);

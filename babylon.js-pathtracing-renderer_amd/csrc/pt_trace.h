@@ -94,9 +94,12 @@ PT_D f3 sphereNormal(const TraceArgs& a, f3 rayO, f3 rayD, const Hit& h)
 // wave's base (MegaStack BASE), the sphere normal is formed after the walk (kNormalAfter)
 // `walked` (pt_raycast alone; the path kernels pass none, and inlined the copy is no code): the walk's result, for
 // the triangle and the barycentrics of a mesh hit
+// `start` (the bounded queries of pt_raycast.hip alone; the path kernels pass none): where hitT starts, the GLSL's
+// INFINITY by default. It bounds the analytic tests and, through h.t, the walk: the boxes it culls as well as the
+// triangles it takes. When nothing is nearer, h.id stays -1 and h.t is `start`.
 template <int PROG, bool COUNT, int LS, bool SLIM>
 PT_D void sceneIntersect(const TraceArgs& a, f3 rayO, f3 rayD, Hit& h, float2* lds, unsigned lane_slot,
-                         unsigned deep, Cnt& cnt, bool firstHit, BvhResult* walked = nullptr)
+                         unsigned deep, Cnt& cnt, bool firstHit, BvhResult* walked = nullptr, float start = kINF)
 {
     // `firstHit`: of this segment's hit only "the light / nothing / something else" is read (bounceStep
     // decides which segments). The walk may then stop at the first triangle closer than the analytic
@@ -111,7 +114,7 @@ PT_D void sceneIntersect(const TraceArgs& a, f3 rayO, f3 rayD, Hit& h, float2* l
     // the walk, same results
     f3 sn;
     PT_SEC(cnt, 4);
-    analyticNearest<PROG>(a, rayO, rayD, h, sn);
+    analyticNearest<PROG>(a, rayO, rayD, h, sn, start);
     PT_SEC(cnt, 1);
     if (!kHasMesh<PROG>) { analyticAttributes<PROG>(a, h, sn); PT_SEC(cnt, 3); return; }
 

@@ -23,6 +23,7 @@
 //   engine.denoise(beautyRT, normalRT, albedoRT, dstRT, opts) -> pt_denoise (extension: a-trous filter over them)
 //   effect.setMomentTarget(momentsRT)             -> pt_set_moment_target (extension: accumulated luminance moments)
 //   effect.castRays(origins, dirs) / effect.pick(x, y) -> pt_cast_rays (extension: ray queries against the bound scene)
+//   effect.castRays(origins, dirs, {tMax, occluded}) / effect.lineOfSight(p, q) -> pt_cast_rays_ex (a bound, occlusion)
 //   engine.denoiseVariance(beautyRT, normalRT, albedoRT, momentsRT, dstRT, opts) -> pt_denoise_variance
 //   engine.encodeCanvasJPEG(quality, subsampling, optimize) -> pt_canvas_encode_jpeg_opt (extension: the canvas as a JPEG file)
 //   engine.encodeCanvasPNG(colour, filter) -> pt_canvas_encode_png (extension: the canvas as a PNG file, lossless)
@@ -521,11 +522,25 @@ function install(BABYLON, opts) {
     // data textures bound now, on world-space rays (3 floats per ray each). Returns an ArrayBuffer of 64-byte records
     // (include/pt.h pt_ray_hit: t, object_id, type, triangle | normal.xyz, bary_u | color.xyz, bary_v | uv.xy, 0, 0),
     // or null when the call fails (reported through onError)
-    castRays(origins, dirs) {
+    // With `opts` (pt_cast_rays_ex, host memory): { tMax: Float32Array, one per ray } bounds each ray - hitT starts at
+    // min(INFINITY, tMax), so nothing at tMax or beyond is taken (the walk's bound, INTEGRATION.md "Ray queries") -
+    // and { occluded: true } returns one byte per ray instead, 1 where the bounded query reports an object.
+    castRays(origins, dirs, opts) {
       if (!this._pt) return null;
-      const r = addon.pt_cast_rays(this._pt, origins, dirs);
+      const tMax = opts && opts.tMax !== undefined ? opts.tMax : null, occluded = !!(opts && opts.occluded);
+      const r = tMax === null && !occluded ? addon.pt_cast_rays(this._pt, origins, dirs)
+        : addon.pt_cast_rays_ex(this._pt, origins, dirs, tMax, occluded);
       if (typeof r === 'number') { check(this._ctx, r, 'castRays'); return null; }
       return r;
+    }
+    // ... whether nothing occludes the open segment from p[i] to q[i] (3 floats per point each): castRays with
+    // dirs = q - p formed in float32, tMax = 1 and occluded. Returns an Array of booleans, or null on failure.
+    lineOfSight(p, q) {
+      const n = Math.floor(p.length / 3);
+      const d = new Float32Array(p.length), t = new Float32Array(n).fill(1);
+      for (let i = 0; i < p.length; i++) d[i] = Math.fround(Math.fround(q[i]) - Math.fround(p[i]));
+      const r = this.castRays(Float32Array.from(p), d, { tMax: t, occluded: true });
+      return r ? Array.from(new Uint8Array(r), (v) => v === 0) : null;
     }
     // ... the pinhole ray through the centre of pixel (x, y) (row 0 the bottom one, as gl_FragCoord; width x height
     // default to uResolution), formed in float32 from uCameraMatrix, uULen and uVLen as the shaders' main() forms its

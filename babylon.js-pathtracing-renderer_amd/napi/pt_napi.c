@@ -613,6 +613,34 @@ static napi_value CastRays(napi_env env, napi_callback_info info)
     const int rc = pt_cast_rays((pt_effect*)handle(env, a[0]), org, dir, n, (pt_ray_hit*)hits);
     return rc == PT_OK ? ab : num(env, rc);
 }
+/* pt_cast_rays_ex(effect, origins, dirs, tMax: Float32Array (1 per ray) | null | undefined, occluded: boolean) ->
+ * ArrayBuffer of pt_ray_hit records (64 B per ray), or of one byte per ray (1 or 0) when `occluded`; the status
+ * when the call fails. Host memory (PT_RAYS_HOST). */
+static napi_value CastRaysEx(napi_env env, napi_callback_info info)
+{
+    napi_value a[MAXARGS]; if (args(env, info, a, 5) < 0) return NULL;
+    size_t lo, ld, lt = 0;
+    const float* org = (const float*)bytes_of(env, a[1], &lo);
+    const float* dir = (const float*)bytes_of(env, a[2], &ld);
+    if (lo != ld || lo % 12 != 0 || lo / 12 > 0x7fffffffu) return num(env, PT_ERR_ARG);
+    const int n = (int)(lo / 12);
+    napi_valuetype vt;
+    CHECK(napi_typeof(env, a[3], &vt));
+    const float* tmax = NULL;
+    if (vt != napi_undefined && vt != napi_null) {
+        tmax = (const float*)bytes_of(env, a[3], &lt);
+        if (lt != (size_t)n * 4) return num(env, PT_ERR_ARG);
+    }
+    bool occluded = false;
+    CHECK(napi_coerce_to_bool(env, a[4], &a[4]));
+    CHECK(napi_get_value_bool(env, a[4], &occluded));
+    void* out = NULL;
+    napi_value ab;
+    CHECK(napi_create_arraybuffer(env, (size_t)n * (occluded ? 1 : sizeof(pt_ray_hit)), &out, &ab));
+    const pt_ray_query q = { org, dir, n ? tmax : NULL, out, n, occluded ? PT_RAYS_OCCLUDED : PT_RAYS_CLOSEST, PT_RAYS_HOST };
+    const int rc = pt_cast_rays_ex((pt_effect*)handle(env, a[0]), &q);
+    return rc == PT_OK ? ab : num(env, rc);
+}
 /* pt_bvh_build(aabbIn: Float32Array (9 per triangle), work: Uint32Array, out: Float32Array) -> node count */
 static napi_value BvhBuild(napi_env env, napi_callback_info info)
 {
@@ -699,7 +727,7 @@ static napi_value Init(napi_env env, napi_value exports)
         { "pt_set_counting", SetCounting }, { "pt_read_counters", ReadCounters }, { "pt_reset_counters", ResetCounters }, { "pt_queue_stats", QueueStats }, { "pt_cont_stats", ContStats }, { "pt_fuse_stats", FuseStats },
         { "pt_set_feature_targets", SetFeatureTargets }, { "pt_denoise", Denoise },
         { "pt_set_moment_target", SetMomentTarget }, { "pt_denoise_variance", DenoiseVariance },
-        { "pt_cast_rays", CastRays },
+        { "pt_cast_rays", CastRays }, { "pt_cast_rays_ex", CastRaysEx },
         { "pt_bvh_build", BvhBuild }, { "pt_bvh_build_gpu", BvhBuildGpu },
         { "pt_jpeg_size", JpegSize }, { "pt_jpeg_decode_rgba8", JpegDecode }, { "pt_version", Version },
     };

@@ -42,7 +42,7 @@ SYMBOLS = [
     "pt_canvas_encode_png", "pt_target_encode_hdr", "pt_targets_encode_exr", "pt_targets_encode_exr_begin", "pt_canvas_encode_jpeg_begin", "pt_canvas_encode_png_begin", "pt_target_encode_hdr_begin", "pt_canvas_read_begin", "pt_job_poll", "pt_job_finish", "pt_job_cancel", "pt_job_stats",
     "pt_write_pixels",
     "pt_set_row_partition", "pt_set_output_partition", "pt_canvas_wrap", "pt_set_backend", "pt_set_bvh_layout", "pt_bvh_layout_used", "pt_set_stream", "pt_texture_device_ptr", "pt_last_render_ms", "pt_timing_begin", "pt_timing_end", "pt_timing_latency",
-    "pt_set_counting", "pt_read_counters", "pt_reset_counters", "pt_queue_stats", "pt_cont_stats", "pt_fuse_stats", "pt_set_feature_targets", "pt_denoise", "pt_set_moment_target", "pt_denoise_variance", "pt_cast_rays", "pt_math_probe", "pt_math_exhaustive", "pt_bvh_build", "pt_bvh_build_gpu", "pt_jpeg_size", "pt_jpeg_decode_rgba8", "pt_version",
+    "pt_set_counting", "pt_read_counters", "pt_reset_counters", "pt_queue_stats", "pt_cont_stats", "pt_fuse_stats", "pt_set_feature_targets", "pt_denoise", "pt_set_moment_target", "pt_denoise_variance", "pt_cast_rays", "pt_cast_rays_ex", "pt_math_probe", "pt_math_exhaustive", "pt_bvh_build", "pt_bvh_build_gpu", "pt_jpeg_size", "pt_jpeg_decode_rgba8", "pt_version",
 ]
 
 
@@ -61,6 +61,29 @@ RAY_HIT = np.dtype([("t", "<f4"), ("object_id", "<i4"), ("type", "<i4"), ("trian
                     ("bary_u", "<f4"), ("color", "<f4", (3,)), ("bary_v", "<f4"), ("uv", "<f4", (2,)),
                     ("reserved", "<f4", (2,))])
 RAY_MISS_T = np.float32(1000000.0)   # the shaders' INFINITY
+RAYS_CLOSEST, RAYS_OCCLUDED = 0, 1   # pt_ray_query.mode
+RAYS_HOST, RAYS_DEVICE = 0, 1        # pt_ray_query.memory
+
+
+class RayQuery(ctypes.Structure):
+    """pt_ray_query (include/pt.h)."""
+    _fields_ = [("origins", ctypes.c_void_p), ("dirs", ctypes.c_void_p), ("t_max", ctypes.c_void_p), ("out", ctypes.c_void_p),
+                ("n", ctypes.c_int), ("mode", ctypes.c_int), ("memory", ctypes.c_int)]
+
+
+def ray_hits(records):
+    """A host copy of a device query's (n, 16) float32 records - Effect.cast_rays on torch tensors - viewed as
+    RAY_HIT: a torch tensor (copied to the host here, which waits for the work queued on it) or a numpy array."""
+    if hasattr(records, "detach"):
+        records = records.detach().cpu().numpy()
+    a = np.ascontiguousarray(records, np.float32)
+    if a.ndim != 2 or a.shape[1] != 16:
+        raise ValueError("ray_hits: (n, 16) float32 records")
+    return a.view(RAY_HIT).reshape(-1)
+
+
+def _is_tensor(x):
+    return type(x).__module__.split(".")[0] == "torch"
 
 
 def lib():
@@ -127,6 +150,7 @@ def lib():
         "pt_set_moment_target": ([vp, vp], i32),
         "pt_denoise_variance": ([vp, vp, vp, vp, vp, vp, i32, ctypes.c_float, ctypes.c_float, i32], i32),
         "pt_cast_rays": ([vp, vp, vp, i32, vp], i32),
+        "pt_cast_rays_ex": ([vp, ctypes.POINTER(RayQuery)], i32),
         "pt_queue_stats": ([vp, ctypes.POINTER(ctypes.c_uint32)], i32), "pt_version": ([], ctypes.c_char_p),
     }
     for name, (args, res) in sig.items():
@@ -717,18 +741,81 @@ class Effect:
                           "setMomentTarget")
 
 
-    def cast_rays(self, origins, dirs):
-        """MI355X extension (pt_cast_rays): SceneIntersect of this path-tracing effect's program, with the uniforms
-        and data textures bound now, on world-space rays. `origins` and `dirs` are (n, 3) float32; returns n RAY_HIT
-        records (t in units of |dir|; on a miss t = RAY_MISS_T, object_id -1, type -100, triangle -1, the rest 0)."""
+    def cast_rays(self, origins, dirs, t_max=None):
+        """MI355X extension (pt_cast_rays, pt_cast_rays_ex): SceneIntersect of this path-tracing effect's program, with
+        the uniforms and data textures bound now, on world-space rays. `origins` and `dirs` are (n, 3) float32; returns
+        n RAY_HIT records (t in units of |dir|; on a miss t = RAY_MISS_T, object_id -1, type -100, triangle -1, the
+        rest 0). `t_max` ((n,) float32, or one number for every ray): hitT starts at min(INFINITY, t_max) - the bound
+        of the walk, INTEGRATION.md "Ray queries" - so nothing at t_max or beyond is taken; NaN, inf and anything
+        >= 1000000 are no bound.
+        Given torch tensors on the engine's device (contiguous float32; t_max a tensor too, or None) the query takes
+        the device route: nothing is copied or awaited, and the records come back as an (n, 16) float32 tensor
+        (ray_hits() views a host copy as RAY_HIT). The call is queued on the context's stream: what produced the
+        rays must be ordered before it, and the tensors kept alive and untouched until a sync."""
+        if _is_tensor(origins) or _is_tensor(dirs) or _is_tensor(t_max):
+            return self._cast_device(origins, dirs, t_max, RAYS_CLOSEST)
+        return self._cast_host(origins, dirs, t_max, RAYS_CLOSEST)
+
+    def occluded(self, origins, dirs, t_max=None):
+        """Whether anything lies on each ray before t_max (pt_cast_rays_ex, PT_RAYS_OCCLUDED): a bool array, True
+        where cast_rays(origins, dirs, t_max) would report an object. The walk may stop at the first occluder. Torch
+        tensors on the engine's device take the device route and give a (n,) uint8 tensor of 1s and 0s, without a
+        sync (see cast_rays)."""
+        if _is_tensor(origins) or _is_tensor(dirs) or _is_tensor(t_max):
+            return self._cast_device(origins, dirs, t_max, RAYS_OCCLUDED)
+        return self._cast_host(origins, dirs, t_max, RAYS_OCCLUDED).astype(bool)
+
+    def line_of_sight(self, p, q, t_max=1.0):
+        """True where nothing occludes the open segment from p to q ((n, 3) each): occluded() with dirs = q - p,
+        formed in float32, and t_max = 1 (a smaller one shortens the segment: a host that aims at a surface point
+        passes, say, 0.999, since a surface within an ulp or so of the end may or may not count)."""
+        p = np.ascontiguousarray(p, np.float32).reshape(-1, 3)
+        q = np.ascontiguousarray(q, np.float32).reshape(-1, 3)
+        if p.shape != q.shape:
+            raise ValueError("line_of_sight: p and q must both be (n, 3)")
+        return ~self.occluded(p, q - p, t_max)
+
+    def _cast_host(self, origins, dirs, t_max, mode):
         o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
         d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
         if o.shape != d.shape:
             raise ValueError("cast_rays: origins and dirs must both be (n, 3)")
-        hits = np.zeros(o.shape[0], RAY_HIT)
-        self.engine.check(lib().pt_cast_rays(self.handle, o.ctypes.data if len(o) else None, d.ctypes.data if len(d) else None,
-                                             o.shape[0], hits.ctypes.data if len(o) else None), "pt_cast_rays")
-        return hits
+        n = o.shape[0]
+        out = np.zeros(n, RAY_HIT if mode == RAYS_CLOSEST else np.uint8)
+        if t_max is None and mode == RAYS_CLOSEST:
+            self.engine.check(lib().pt_cast_rays(self.handle, o.ctypes.data if n else None, d.ctypes.data if n else None,
+                                                 n, out.ctypes.data if n else None), "pt_cast_rays")
+            return out
+        t = None
+        if t_max is not None:
+            t = np.ascontiguousarray(np.broadcast_to(np.asarray(t_max, np.float32), (n,)) if np.ndim(t_max) == 0
+                                     else np.asarray(t_max, np.float32).reshape(-1))
+            if t.shape != (n,):
+                raise ValueError("cast_rays: t_max must be one number or (n,)")
+        q = RayQuery(o.ctypes.data if n else None, d.ctypes.data if n else None, t.ctypes.data if t is not None and n else None,
+                     out.ctypes.data if n else None, n, mode, RAYS_HOST)
+        self.engine.check(lib().pt_cast_rays_ex(self.handle, ctypes.byref(q)), "pt_cast_rays_ex")
+        return out
+
+    def _cast_device(self, origins, dirs, t_max, mode):
+        import torch
+        given = [origins, dirs] + ([t_max] if t_max is not None else [])
+        for x in given:
+            if not _is_tensor(x) or x.dtype != torch.float32 or not x.is_contiguous():
+                raise ValueError("cast_rays: the device route takes contiguous float32 torch tensors")
+            if x.device.type != "cuda" or x.device.index != self.engine.device:
+                raise ValueError("cast_rays: the tensors must be on the engine's device")
+        if origins.dim() != 2 or origins.shape[1] != 3 or origins.shape != dirs.shape:
+            raise ValueError("cast_rays: origins and dirs must both be (n, 3)")
+        n = origins.shape[0]
+        if t_max is not None and tuple(t_max.shape) != (n,):
+            raise ValueError("cast_rays: t_max must be (n,)")
+        out = (torch.empty((n, 16), dtype=torch.float32, device=origins.device) if mode == RAYS_CLOSEST
+               else torch.empty((n,), dtype=torch.uint8, device=origins.device))
+        q = RayQuery(origins.data_ptr() if n else None, dirs.data_ptr() if n else None,
+                     t_max.data_ptr() if t_max is not None and n else None, out.data_ptr() if n else None, n, mode, RAYS_DEVICE)
+        self.engine.check(lib().pt_cast_rays_ex(self.handle, ctypes.byref(q)), "pt_cast_rays_ex")
+        return out
 
     def _uniform(self, name, n):
         """The last value this effect's float uniform `name` was given, as n float32 (GLSL's zeros while unset)."""

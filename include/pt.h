@@ -581,6 +581,46 @@ typedef struct pt_ray_hit {          /* 64 bytes, one line per ray */
     float   reserved[2];             /* +0.0 */
 } pt_ray_hit;
 int pt_cast_rays(pt_effect* fx, const float* origins, const float* dirs, int n, pt_ray_hit* hits);
+/* Ray queries with a distance bound, an occlusion mode and device-resident rays. pt_cast_rays is the
+ * PT_RAYS_HOST + PT_RAYS_CLOSEST + t_max == NULL case of it, and stays as it is to the bit.
+ * The bound. With t_max given, ray i is SceneIntersect with hitT starting at min(INFINITY, t_max[i]) instead of
+ * INFINITY - the GLSL's min, y < x ? y : x - and nothing else changed. So a NaN, an infinite or any t_max >= 1000000.0
+ * is no bound; and since every object test is `d < hitT`, strict, a t_max of 0, of -1, or of exactly the unbounded
+ * hit's t is a miss. A ray that takes no object gets pt_cast_rays' miss record: t = 1000000.0 (not t_max), ids
+ * -1 / -100 / -1, the rest +0. t is in units of |dir|: with dirs = q - p and t_max = 1 the query is the open segment
+ * from p to q.
+ * The bound is the walk's, not a filter on the unbounded record. For the analytic objects the two are the same (a
+ * running minimum under a strict `<`). For the mesh they are not: the lower hitT also culls boxes, so a triangle whose
+ * t is below the bound is not found when the slab test of its leaf (or of a node above it) gives a distance that is
+ * not - which happens within an ulp or so of the bound, on all three BVH layouts alike, and is what the GLSL with
+ * that start would do. A surface that close to the segment's end may or may not count, as in any ray tracer: a host
+ * that aims at a surface point shortens the segment.
+ * PT_RAYS_OCCLUDED: out[i] = 1 iff the bounded closest-hit record of ray i has object_id >= 0, else 0; which object
+ * is not said. The walk may stop at the first occluder; the flag does not depend on whether it does, nor on the
+ * BVH layout.
+ * PT_RAYS_HOST: pt_cast_rays' contract - host pointers, context-owned staging, chunks, synchronous - with 4 B more
+ * per ray going in when t_max is given; OCCLUDED copies back 1 B per ray.
+ * PT_RAYS_DEVICE: origins, dirs, t_max and out are memory of the context's device (a torch tensor's data_ptr(),
+ * say). The call enqueues on the context's stream (pt_set_stream applies) after everything queued so far and returns
+ * without synchronising; there is no staging copy - the kernel reads the caller's rays and writes the caller's
+ * output, one launch per 262,144 rays at pointer offsets, with a context-owned slab for the walk's deep stack levels
+ * only. The caller keeps all buffers alive and untouched until it has synchronised (pt_sync, or its own stream), and
+ * orders what produced the rays before the call (the context's stream, or an earlier synchronise). out for CLOSEST
+ * must be 16-byte aligned (the records are written as 16-byte stores); origins, dirs and t_max 4-byte aligned.
+ * Everything pt_cast_rays promises holds for both: no render target observed; no counter, statistic, cost table, tile
+ * order or timing window moved; the draws' slabs never touched; a draw after it gives the bits it gives without it.
+ * Errors as pt_cast_rays, before any device work; also PT_ERR_ARG for a NULL q, an unknown mode or memory, or a
+ * misaligned device pointer. n == 0 is PT_OK and touches nothing. PT_ERR_UNSUPPORTED: a context of several parts. */
+enum { PT_RAYS_CLOSEST = 0, PT_RAYS_OCCLUDED = 1 };     /* pt_ray_query::mode */
+enum { PT_RAYS_HOST = 0, PT_RAYS_DEVICE = 1 };          /* pt_ray_query::memory: where every pointer of the query lives */
+typedef struct pt_ray_query {
+    const float* origins;            /* [3n] */
+    const float* dirs;               /* [3n] */
+    const float* t_max;              /* [n], or NULL: no bound */
+    void*        out;                /* CLOSEST: pt_ray_hit[n]; OCCLUDED: uint8_t[n], each 1 or 0 */
+    int          n, mode, memory;
+} pt_ray_query;
+int pt_cast_rays_ex(pt_effect* fx, const pt_ray_query* q);
 /* Device self-test of the pinned GLSL built-ins (ops as the oracle's pto_math_probe). */
 int pt_math_probe(pt_ctx* ctx, int op, const float* x, const float* y, float* out, int n);
 /* Exhaustive device self-test of a fast built-in sequence against the IEEE operation it replaces,
